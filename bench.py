@@ -7,6 +7,14 @@ rho0 = lambda/5, u0 = 0, theta0 = mean(y), fixed-iteration mode (the stopping
 test is evaluated but not acted on), PCG theta-solves warm-started at
 rtol 1e-10. Inputs are resident in HBM before timing starts.
 
+A plain run sets up, warms up, times ``--steps`` steps in a region without per-launch events and prints the
+line (``ms_per_step`` = that region's time / steps). ``--full`` adds what takes runs of its own: the per-kernel
+table and roofline (a second region of the same length with HIP events around every launch), the Jacobi-PCG
+leg, the CPU baseline and, at N > 1, the independent fits. ``--dump-outputs DIR`` writes what the timed call
+left, right after it: theta (whole up to 32 MiB, else at 2^20 nodes drawn once from a generator seeded with
+synth.SEED, their indices beside them), and the call's statistics (iters, rho, r_norm, s_norm, eps_pri,
+eps_dual, dtheta_max, pcg_iters), as float64 ``DIR/<name>.npy``.
+
 Other BASELINE configs: ``--dims 2 --size 1024`` (config 2), ``--dims 3 --size 256`` (config 3),
 ``--dims 4 --size 128`` (config 5 on one GPU) and ``--mode cv`` (config 4's work item: a CV fold's
 warm-started lambda chunk on 2048^2 with a 0/1 fold mask W, so the theta-solve is Jacobi-PCG).
@@ -14,7 +22,7 @@ warm-started lambda chunk on 2048^2 with a 0/1 fold mask W, so the theta-solve i
 Multi-GPU (one process per GPU; ``--gpus N`` starts the N rank processes itself when it is not run
 under torchrun). At N > 1 the headline is the metric's own definition: ONE 512^3 mesh
 slab-decomposed over the N GPUs (``scaling: strong``; the whole loop inside libmvtv with RCCL on the
-solver stream). Before it every rank also fits its own independent 512^3 mesh (noise seed + rank, the
+solver stream). With ``--full`` every rank first also fits its own independent 512^3 mesh (noise seed + rank, the
 embarrassingly parallel sharding of the north star); that aggregate is reported beside the headline as
 ``independent_fits`` (``scaling: weak``). One RCCL per process: torch.distributed runs on gloo (host
 barriers, max-over-ranks time, the 128-byte RCCL id; torch's own RCCL is never initialised) and every
@@ -115,13 +123,20 @@ def parse():
                     help="theta-solve: auto = spectral (exact DCT solve) where it applies, else the spectrally "
                          "preconditioned PCG (2-3-5-7 meshes), else Jacobi-PCG; pcg = Jacobi-PCG; "
                          "spectral = the exact solve (--mode cv: the spectrally preconditioned PCG)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline value: the per-kernel table and roofline (a second timed region with "
+                         "per-launch HIP events), the Jacobi-PCG leg, the CPU baseline and, at N > 1, the independent "
+                         "fits. Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the timed path left (theta, or a fixed seeded sample of a "
+                         "large one; rho and the run's statistics) as DIR/<name>.npy")
     ap.add_argument("--pcg-steps", type=int, default=10,
-                    help="steps of the secondary Jacobi-PCG leg reported beside the main one (0 = skip)")
+                    help="--full: steps of the secondary Jacobi-PCG leg reported beside the main one (0 = skip)")
     ap.add_argument("--mode", choices=["auto", "independent", "slab", "cv"], default="auto",
                     help="auto: N = 1 one fit; N > 1 one mesh slab-decomposed over the GPUs (strong scaling, the "
                          "metric) with the independent fits per GPU (weak scaling) reported beside it. "
                          "independent / slab: only that one")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
     ap.add_argument("--mesh", type=str, default="",
                     help="--mode slab: an explicit mesh 'm0,m1,...' instead of size^dims (e.g. 512,512,64: one rank's "
                          "share of 512^3 at 8 GPUs, run at world 1 with MVTV_SLAB_DISTRIBUTED=1)")
@@ -312,6 +327,31 @@ def cpu_baseline(m, lam, pcg_iters, planes, full=False):
 
 METRIC = "ADMM iters/sec on 512^3 fp64 mesh; achieved HBM GB/s vs peak at 1/2/4/8 GPUs"
 
+DUMP_FULL_BYTES = 32 << 20   # --dump-outputs: a theta up to this size is written whole, a larger one sampled
+DUMP_SAMPLE = 1 << 20        # ... at this many nodes, drawn once from a generator seeded with DUMP_SEED
+DUMP_SEED = 0x4D565456       # (= synth.SEED)
+_STAT_KEYS = ("iters", "rho", "r_norm", "s_norm", "eps_pri", "eps_dual", "dtheta_max", "pcg_iters")
+
+
+def _sample_index(n):
+    """The nodes of an n-node theta that --dump-outputs writes: all of them, or the fixed seeded sample (sorted)."""
+    if 8 * n <= DUMP_FULL_BYTES:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, size=DUMP_SAMPLE, dtype=np.int64))
+
+
+def _dump(dirname, **arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float64."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, v in arrays.items():
+        if v is not None:
+            np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
+
+
+def _stats_array(st):
+    """A run's statistics (the dict the timed call returns) in the order of _STAT_KEYS."""
+    return np.array([float(st[k]) for k in _STAT_KEYS])
+
 
 def _roofline(tim):
     """The dominant kernel (by time) of a timing table and its achieved algorithmic GB/s."""
@@ -375,14 +415,22 @@ def slab_main(a, D, comm=None):
         t1 = time.perf_counter()
         D.barrier()
         g_elapsed, = D.allreduce([t1 - t0], "max")
-        S.P.timing(True)
-        t2 = time.perf_counter()
-        S.run(lam, fixed_iters=a.steps)
-        t3 = time.perf_counter()
-        D.barrier()
-        tim = S.P.timings()
-        S.P.timing(False)
-        ev_elapsed, = D.allreduce([t3 - t2], "max")
+        if a.dump_outputs:   # every rank its owned planes
+            th = S.theta_owned()
+            idx = _sample_index(th.size)
+            _dump(a.dump_outputs, **{f"theta_rank{D.rank}": th if idx is None else th[idx],
+                                     f"theta_rank{D.rank}_index": idx, f"stats_rank{D.rank}": _stats_array(st)})
+            del th
+        tim, ev_elapsed = {}, None
+        if a.full:
+            S.P.timing(True)
+            t2 = time.perf_counter()
+            S.run(lam, fixed_iters=a.steps)
+            t3 = time.perf_counter()
+            D.barrier()
+            tim = S.P.timings()
+            S.P.timing(False)
+            ev_elapsed, = D.allreduce([t3 - t2], "max")
         nranks = D.world
         rccl_ranks = comm.size if comm.kind == "rccl" else 0
         if comm.kind == "ipc":
@@ -399,9 +447,13 @@ def slab_main(a, D, comm=None):
         if a.warmup > 0:
             slab.run_local_group(m, y, deltas, lam, R, fixed_iters=a.warmup)
         t0 = time.perf_counter()
-        outs, _ = slab.run_local_group(m, y, deltas, lam, R, fixed_iters=a.steps)
+        outs, th = slab.run_local_group(m, y, deltas, lam, R, fixed_iters=a.steps)
         t1 = time.perf_counter()
         st, tim = outs[0], {}
+        if a.dump_outputs:
+            idx = _sample_index(th.size)
+            _dump(a.dump_outputs, theta=th if idx is None else th[idx], theta_index=idx, stats=_stats_array(st))
+        del th
         transport = f"in-process loopback, {R} ranks on one GPU"
         g_elapsed, nranks, rccl_ranks = t1 - t0, R, 0
         ev_elapsed = None
@@ -427,7 +479,8 @@ def slab_main(a, D, comm=None):
         "roofline": _roofline(tim), "kernels_rank0": per,
         "timing": ("value from an event-free region; kernels_rank0 / roofline from a second region of the same "
                    f"length with per-launch HIP events ({a.steps / ev_elapsed:.2f} it/s with them)")
-        if ev_elapsed else "no per-kernel events (in-process ranks)",
+        if ev_elapsed else ("no per-kernel events (--full times them in a second region)" if D.world > 1 or R == 1
+                            else "no per-kernel events (in-process ranks)"),
         "residuals": {"r_norm": st["r_norm"], "s_norm": st["s_norm"]}, "cpu_baseline": None}
 
 
@@ -503,18 +556,23 @@ def cv_main(a, D):
             P.timing(False)
         return t1 - t0, tm
     elapsed, _ = timed(False)
-    elapsed_ev, tims = timed(True)
-    t0, t1 = 0.0, elapsed_ev
+    if a.dump_outputs:   # per item: rho after each lambda of the chunk, and every lambda's statistics
+        _dump(a.dump_outputs, **{f"rhos_rank{D.rank}": np.array([o[1] for o in out]),
+                                 f"stats_rank{D.rank}": np.array([[_stats_array(st) for st in o[2]] for o in out])})
     g_elapsed, = D.allreduce([elapsed], "max")
     stats = [o[2] for o in out]
     kbar = sum(st["pcg_iters"] for sts in stats for st in sts) / (steps * B)
-    tim = {k: dict(ms=sum(t[k]["ms"] for t in tims), launches=sum(t[k]["launches"] for t in tims),
-                   bytes_per_launch=tims[0][k]["bytes_per_launch"]) for k in tims[0]}
-    roof = _roofline(tim)
     N = probs[0].N
-    roof["mall_resident"] = 8 * N * 7 < 256 * 2 ** 20
-    moved = sum(v["bytes_per_launch"] * v["launches"] for v in tim.values())
-    if B > 1:
+    rhos = [float(o[1][-1]) for o in out]
+    elapsed_ev, tim, roof, moved = None, {}, None, None
+    if a.full:
+        elapsed_ev, tims = timed(True)
+        tim = {k: dict(ms=sum(t[k]["ms"] for t in tims), launches=sum(t[k]["launches"] for t in tims),
+                       bytes_per_launch=tims[0][k]["bytes_per_launch"]) for k in tims[0]}
+        roof = _roofline(tim)
+        roof["mall_resident"] = 8 * N * 7 < 256 * 2 ** 20
+        moved = sum(v["bytes_per_launch"] * v["launches"] for v in tim.values())
+    if a.full and B > 1:
         # the items' launches overlap, so a launch's duration is shared with other items' kernels: the roofline
         # object is the whole GPU's, the algorithmic bytes of every launch of the event-free region over its time
         per_kernel = dict(roof, note="dominant kernel's launch time while the items run concurrently")
@@ -522,11 +580,10 @@ def cv_main(a, D):
         roof = {"bound": "hbm", "kernel": f"all launches of the {B} concurrent items", "achieved": round(ach, 1),
                 "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBPS, 4), "traffic": None,
                 "mall_resident": per_kernel["mall_resident"], "dominant_kernel_concurrent": per_kernel}
-    else:
+    elif a.full:
         roof["note"] = "per-launch time of the dominant kernel"
     kern = {k: dict(avg_ms=round(v["ms"] / v["launches"], 4), launches=v["launches"]) for k, v in tim.items()
             if v["launches"]}
-    rhos = [float(o[1][-1]) for o in out]
     for P in probs:
         P.close()
     if D.rank != 0:
@@ -548,9 +605,11 @@ def cv_main(a, D):
         "roofline": roof,
         "aggregate_hbm": {"bytes": moved, "GBps": round(moved / elapsed / 1e9, 1),
                           "frac": round(moved / elapsed / 1e9 / HBM_PEAK_GBPS, 4),
-                          "note": "algorithmic bytes of every launch of the rank's items / the rank's wall time"},
+                          "note": "algorithmic bytes of every launch of the rank's items / the rank's wall time"}
+        if a.full else None,
         "with_kernel_events": {"ms_per_step": round(elapsed_ev / steps * 1e3, 3),
-                               "note": "the same region timed with HIP events around every launch (roofline)"},
+                               "note": "the same region timed with HIP events around every launch (roofline)"}
+        if a.full else None,
         "kernels": kern, "cpu_baseline": None}
 
 
@@ -577,7 +636,9 @@ def independent_main(a, D, comm=None):
     # from an event-free timed region and the per-kernel table from a second region of the same length right after
     # it. Round 6: every mesh (the 512^3 headline's events cost ~1 %; MVTV_BENCH_EVENTS_IN_VALUE=1: one region
     # with the events in it for meshes above 2^24 nodes, the round-5 timing)
-    event_free = P.N <= (1 << 24) or os.environ.get("MVTV_BENCH_EVENTS_IN_VALUE", "0") in ("", "0")
+    # Without --full there is the event-free region only: no per-kernel table, roofline, PCG leg or CPU baseline.
+    event_free = (not a.full or P.N <= (1 << 24)
+                  or os.environ.get("MVTV_BENCH_EVENTS_IN_VALUE", "0") in ("", "0"))
     D.barrier()
     P.timing(not event_free)
     t0 = time.perf_counter()
@@ -585,10 +646,16 @@ def independent_main(a, D, comm=None):
     t1 = time.perf_counter()
     D.barrier()
     elapsed = t1 - t0
-    if event_free:
+    if a.dump_outputs:   # the state the timed call left, before any later region moves it on
+        idx = _sample_index(P.N)
+        name = "theta" if D.world == 1 else f"theta_rank{D.rank}"
+        _dump(a.dump_outputs, **{name: P.state_get(want_u=False)[0] if idx is None else P.fitted(idx),
+                                 name + "_index": idx,
+                                 name.replace("theta", "stats"): _stats_array(st)})
+    if event_free and a.full:
         P.timing(True)
         P.run(lam, fixed_iters=a.steps, pcg_rtol=a.pcg_rtol, theta_solver=solver)
-    tim = P.timings()
+    tim = P.timings() if a.full else {}
     P.timing(False)
     used = "spectral" if st["theta_solver"] == mv.SOLVER_SPECTRAL else "pcg"
     kbar = st["pcg_iters"] / max(1, a.steps)
@@ -596,7 +663,7 @@ def independent_main(a, D, comm=None):
 
     # secondary leg: the north star's Jacobi-PCG theta-solve on the same state (reported, not the value)
     pcg_leg = None
-    if used == "spectral" and a.pcg_steps > 0:
+    if a.full and used == "spectral" and a.pcg_steps > 0:
         P.run(lam, fixed_iters=1, pcg_rtol=a.pcg_rtol, theta_solver=mv.SOLVER_PCG)   # warm the PCG poll schedule
         D.barrier()
         P.timing(True)
@@ -627,7 +694,6 @@ def independent_main(a, D, comm=None):
     kbar_all /= D.world
 
     roof = _roofline(tim)
-    dom = roof["kernel"]
     per = {}
     for k, v in tim.items():
         if v["launches"]:
@@ -636,16 +702,17 @@ def independent_main(a, D, comm=None):
                           GBps=round(v["bytes_per_launch"] / (avg * 1e-3) / 1e9, 1) if v["bytes_per_launch"] else None)
     N, E = P.N, P.E
     iter_gbps = moved * a.steps / elapsed / 1e9                  # algorithmic bytes of every kernel launched
-    pmc, pmc_src = load_pmc(dom) if (a.dims, a.size) == (3, 512) else (None, None)
-    roof.update(traffic=pmc, traffic_source=pmc_src,
-                timing=("HIP events in a second timed region of the same length (event-free value region)"
-                        if event_free else "HIP events inside the timed region"),
-                # a mesh whose working set fits the 256 MiB Infinity Cache is served partly on-die:
-                # its "HBM" fraction is an upper bound, not an HBM measurement (SURVEY §7 hard part 7)
-                mall_resident=8 * N * 6 < 256 * 2 ** 20)
+    if roof is not None:
+        pmc, pmc_src = load_pmc(roof["kernel"]) if (a.dims, a.size) == (3, 512) else (None, None)
+        roof.update(traffic=pmc, traffic_source=pmc_src,
+                    timing=("HIP events in a second timed region of the same length (event-free value region)"
+                            if event_free else "HIP events inside the timed region"),
+                    # a mesh whose working set fits the 256 MiB Infinity Cache is served partly on-die:
+                    # its "HBM" fraction is an upper bound, not an HBM measurement (SURVEY §7 hard part 7)
+                    mall_resident=8 * N * 6 < 256 * 2 ** 20)
 
     cpu = None
-    if D.world == 1 and not a.no_cpu:
+    if a.full and D.world == 1 and not a.no_cpu:
         planes = a.cpu_planes or max(4, m[-1] // 4)
         try:
             k_cpu = pcg_leg["pcg_iters_mean"] if pcg_leg else kbar   # the oracle's PCG leg runs the GPU's mean count
@@ -677,7 +744,7 @@ def independent_main(a, D, comm=None):
         "roofline": roof,
         "iteration_hbm": {"bytes_per_iter": moved, "GBps": round(iter_gbps, 1),
                           "frac": round(iter_gbps / HBM_PEAK_GBPS, 4),
-                          "survey_bytes_per_iter": 8.0 * (5 * E + 8 * N + 10 * kbar * N)},
+                          "survey_bytes_per_iter": 8.0 * (5 * E + 8 * N + 10 * kbar * N)} if a.full else None,
         "pcg_leg": pcg_leg,
         "kernels": per,
         "residuals": {"r_norm": float(np.sqrt(r2)), "s_norm": float(np.sqrt(s2)), "pcg_unconverged": int(n_unconv)},
@@ -733,7 +800,8 @@ def main():
                 comm = None
             if comm is not None:
                 log(f"rank {D.rank}: RCCL communicator failed, slab loop over the ipc transport")
-        ind = independent_main(a, D, comm)
+        # the independent fits beside the headline are --full's; without it they run only when there is no slab line
+        ind = independent_main(a, D, comm) if a.full else None
         line = None
         if comm is not None:
             try:
@@ -762,7 +830,9 @@ def main():
             if failed:
                 line = None
                 err = err or "slab run failed on another rank"
-        if line is not None:
+        if not a.full and (comm is None or failed):   # every rank agrees on both
+            ind = independent_main(a, D, None)
+        if line is not None and ind is not None:
             line["independent_fits"] = {k: ind[k] for k in ("value", "unit", "ms_per_step", "scaling", "roofline",
                                                             "residuals")}
             line["independent_fits"]["workload"] = (f"one {a.size}^{a.dims} fit per GPU (noise seed + rank), "

@@ -80,6 +80,39 @@ def test_bounded_agreement_after_a_slab_failure():
     assert out[0].startswith("agreed") and "[2.0]" in out[0]
 
 
+def test_dump_outputs_sample_is_fixed_and_files_are_float64(tmp_path):
+    """--dump-outputs: a theta up to 32 MiB is written whole, a larger one at the same 2^20 sorted nodes in every
+    process (seeded), within the mesh; every file is float64 .npy."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench._sample_index(bench.DUMP_FULL_BYTES // 8) is None
+    n = 512 ** 3
+    idx = bench._sample_index(n)
+    assert idx.shape == (bench.DUMP_SAMPLE,) and idx.dtype == np.int64
+    assert idx.min() >= 0 and idx.max() < n and np.all(np.diff(idx) >= 0)
+    code = f"import sys; sys.path.insert(0, {ROOT!r}); import bench; print(int(bench._sample_index({n})[::4097].sum()))"
+    other = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120, cwd=ROOT)
+    assert other.returncode == 0, other.stderr
+    assert int(other.stdout.split()[-1]) == int(idx[::4097].sum())
+    bench._dump(str(tmp_path / "d"), theta=np.arange(5, dtype=np.float32), theta_index=None, stats=[1, 2.5])
+    assert sorted(os.listdir(tmp_path / "d")) == ["stats.npy", "theta.npy"]
+    for name in ("stats", "theta"):
+        assert np.load(tmp_path / "d" / (name + ".npy")).dtype == np.float64
+    assert 8 * (2 * bench.DUMP_SAMPLE + len(bench._STAT_KEYS)) <= 64 << 20 and 2 * bench.DUMP_FULL_BYTES <= 64 << 20
+
+
+def test_plain_run_is_the_default_and_full_is_an_option(monkeypatch):
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert not a.full and a.dump_outputs == "" and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "somewhere"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "somewhere"
+
+
 def test_cpu_baseline_cores_follow_affinity_and_cgroup_quota(monkeypatch):
     """cpu_baseline's threads: the affinity mask capped by cgroup v2 cpu.max (the GPU box grants 16 of 256)."""
     sys.path.insert(0, ROOT)

@@ -10,7 +10,6 @@ The children are started with multiprocessing's spawn (a fresh interpreter each)
 the rendezvous segment's name; the reference theta goes to them through a file."""
 import ctypes as C
 import os
-import socket
 import sys
 
 import numpy as np
@@ -22,12 +21,6 @@ from multivartv_amd.synth import towers  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
 def _fold_mask(m):
     return (np.arange(int(np.prod(m))) % 5 != 2).astype(np.float64)
 
@@ -36,14 +29,14 @@ def _say(rank, msg):
     print(f"[ipc rank {rank}] {msg}", file=sys.stderr, flush=True)
 
 
-def _rank_main(rank, world, port, q, m, lam, iters, ref_path, weighted, fail_rank, t0):
+def _rank_main(rank, world, rdzv, q, m, lam, iters, ref_path, weighted, fail_rank, t0):
     import faulthandler
     faulthandler.dump_traceback_later(100, exit=False)   # a stuck rank shows where it is
     import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    _say(rank, f"up, mesh {m}")
     try:
+        # a file rendezvous: a port picked here and bound by rank 0 seconds later could be taken in between
+        dist.init_process_group("gloo", init_method="file://" + rdzv, rank=rank, world_size=world)
+        _say(rank, f"up, mesh {m}")
         from multivartv_amd import _lib, slab
         deltas = [(1.0 + 2e-4) / v for v in m]
         b = slab.plane_bounds(m[-1], world)
@@ -78,20 +71,21 @@ def _rank_main(rank, world, port, q, m, lam, iters, ref_path, weighted, fail_ran
     except Exception as e:  # noqa: BLE001 (reported to the parent)
         q.put((rank, None, None, repr(e)))
     finally:
-        dist.destroy_process_group()
+        if dist.is_initialized():
+            dist.destroy_process_group()
 
 
 def _run_group(world, m, lam, iters, ref_path, t0, weighted=False, fail_rank=-1, env=None):
     import torch.multiprocessing as mp
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    rdzv = ref_path + ".rdzv"   # under the test's tmp_path: fresh for every group
     env = dict(env or {})
     env.setdefault("MVTV_IPC_TIMEOUT", "60")   # a transport wait that never ends fails the test instead
     old = {k: os.environ.get(k) for k in env}
     os.environ.update(env)
     try:
-        procs = [ctx.Process(target=_rank_main, args=(r, world, port, q, m, lam, iters, ref_path, weighted, fail_rank, t0))
+        procs = [ctx.Process(target=_rank_main, args=(r, world, rdzv, q, m, lam, iters, ref_path, weighted, fail_rank, t0))
                  for r in range(world)]
         for p in procs:
             p.start()
@@ -101,11 +95,22 @@ def _run_group(world, m, lam, iters, ref_path, t0, weighted=False, fail_rank=-1,
                 os.environ.pop(k, None)
             else:
                 os.environ[k] = v
-    res = sorted((q.get(timeout=180) for _ in procs), key=lambda t: t[0])
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    try:
+        res = sorted((q.get(timeout=180) for _ in procs), key=lambda t: t[0])
+        for p in procs:
+            p.join(timeout=60)
+            assert p.exitcode == 0
+    finally:   # a rank still alive here is stuck: end it, so that it cannot outlive the test (or the session's exit)
+        for p in procs:
+            if p.is_alive():
+                p.kill()
+                p.join(timeout=10)
     return res
+
+
+def _no_rank_failed(res):
+    failed = [(rank, exc) for rank, _, _, exc in res if exc is not None]
+    assert not failed, failed   # every rank's error: the first to give up is rarely the one that failed
 
 
 def _one_gpu(m, lam, iters, weighted=False):
@@ -129,6 +134,7 @@ def test_slab_processes_weighted_fold(tmp_path):
     ref = tmp_path / "theta.npy"
     np.save(ref, th)
     res = _run_group(world, m, lam, iters, str(ref), t0, weighted=True)
+    _no_rank_failed(res)
     for rank, o, err, exc in res:
         assert exc is None, (rank, exc)
         assert o["iters"] == iters and o["rho"] == rho
@@ -160,6 +166,7 @@ def test_slab_processes_match_one_gpu(tmp_path, m, world, iters):
     scale = float(np.max(np.abs(th)))
     del th
     res = _run_group(world, m, lam, iters, str(ref), t0)
+    _no_rank_failed(res)
     for rank, o, err, exc in res:
         assert exc is None, (rank, exc)
         assert o["iters"] == st["iters"] and o["rho"] == rho, (rank, o["iters"], st["iters"])

@@ -3,6 +3,7 @@
 set -o pipefail
 R=$GRAFT_REPO_ROOT
 mkdir -p $R/gpurun_out/ab
+BENCH_ARGS="--full ${BENCH_ARGS}"   # the per-kernel table printed below is --full's
 IFS=';' read -ra CASES <<< "$SWEEP"
 i=0
 for c in "${CASES[@]}"; do

@@ -17,7 +17,7 @@ for rep in 1 2; do
     for c in ${CASES:-3:512}; do
       d=${c%%:*}; n=${c##*:}
       f=$OUT/$d.$n.$rep.${e%%=*}
-      env $ev timeout -k 10 200 python bench.py --no-cpu --pcg-steps 0 --steps ${STEPS:-30} --warmup 5 --dims $d --size $n ${BENCH_EXTRA} > $f.json 2> $f.err || { tail -5 $f.err; exit 1; }
+      env $ev timeout -k 10 200 python bench.py --full --no-cpu --pcg-steps 0 --steps ${STEPS:-30} --warmup 5 --dims $d --size $n ${BENCH_EXTRA} > $f.json 2> $f.err || { tail -5 $f.err; exit 1; }
       python -c "import json,sys;d=json.load(open(sys.argv[1]));print(sys.argv[2],d['value'],{k:v['avg_ms'] for k,v in d.get('kernels',{}).items()})" $f.json "$d:$n $e.$rep"
     done
   done

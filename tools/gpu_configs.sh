@@ -11,7 +11,7 @@ fi
 run() {  # name, args...
   local n=$1; shift
   echo "== $n $*" >> $O/progress.log
-  timeout -k 10 400 python bench.py "$@" > $O/$n.json 2> $O/$n.err
+  timeout -k 10 400 python bench.py --full "$@" > $O/$n.json 2> $O/$n.err
 }
 run b512 && run b1024 --dims 2 --size 1024 && run b2048 --dims 2 --size 2048 && run b256 --dims 3 --size 256 && \
 run b128_4d --dims 4 --size 128 --pcg-steps 4 && run bcv --mode cv --steps 40 --warmup 5 && \
@@ -22,7 +22,7 @@ cd /tmp && export TMPDIR=/tmp
 kt() {
   local n=$1; shift
   echo "== kt $n $*" >> $O/progress.log
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/kt_$n -o run --output-format csv -- python3 $R/bench.py --no-cpu "$@" > $O/kt_$n.log 2>&1
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/kt_$n -o run --output-format csv -- python3 $R/bench.py --full --no-cpu "$@" > $O/kt_$n.log 2>&1
 }
 kt b1024 --dims 2 --size 1024 --pcg-steps 2 && kt bcv --mode cv --steps 20 --warmup 2 --cv-batch 1 && \
 kt b128_4d --dims 4 --size 128 --steps 5 --warmup 2 --pcg-steps 0 && kt b256 --dims 3 --size 256 --pcg-steps 0

@@ -35,10 +35,10 @@ for rep in $(seq 1 ${REPS:-2}); do
       f=$O/c$j.$d.$n.$rep
       echo "$e" > $f.case
       if [ "${KT:-0}" = 1 ]; then
-        env $ev timeout -k 10 300 rocprofv3 --kernel-trace -d $f.kt -o run --output-format csv -- python3 $R/bench.py --no-cpu --pcg-steps ${PCG_STEPS:-0} --steps ${STEPS:-20} --warmup 3 --dims $d --size $n ${BENCH_EXTRA} > $f.json 2> $f.err || { tail -5 $f.err; exit 1; }
+        env $ev timeout -k 10 300 rocprofv3 --kernel-trace -d $f.kt -o run --output-format csv -- python3 $R/bench.py --full --no-cpu --pcg-steps ${PCG_STEPS:-0} --steps ${STEPS:-20} --warmup 3 --dims $d --size $n ${BENCH_EXTRA} > $f.json 2> $f.err || { tail -5 $f.err; exit 1; }
         python3 $R/tools/prof_summary.py $f.kt $f.kt.md > /dev/null
       else
-        env $ev timeout -k 10 300 python3 $R/bench.py --no-cpu --pcg-steps ${PCG_STEPS:-0} --steps ${STEPS:-20} --warmup 3 --dims $d --size $n ${BENCH_EXTRA} > $f.json 2> $f.err || { tail -5 $f.err; exit 1; }
+        env $ev timeout -k 10 300 python3 $R/bench.py --full --no-cpu --pcg-steps ${PCG_STEPS:-0} --steps ${STEPS:-20} --warmup 3 --dims $d --size $n ${BENCH_EXTRA} > $f.json 2> $f.err || { tail -5 $f.err; exit 1; }
       fi
       python3 -c "import json,sys;d=json.load(open(sys.argv[1]));k=d.get('kernels',{});print(sys.argv[2],d['value'],d.get('pcg_leg',{}).get('value') if isinstance(d.get('pcg_leg'),dict) else '',json.dumps({a:round(b['avg_ms'],4) for a,b in k.items()}))" $f.json "[$e] $d:$n r$rep"
     done
