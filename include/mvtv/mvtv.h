@@ -275,6 +275,14 @@ mvtv_status mvtv_timing_get(mvtv_problem* prob, int32_t kernel_id, double* total
                             double* bytes_per_launch);
 const char* mvtv_kernel_name(int32_t kernel_id);
 
+/* Launch log (tests; off by default, per calling thread). on != 0: clear the log and record the kernel, grid and
+ * block of every launch this thread makes from now on (the last 8192 are kept); on == 0: stop and clear.
+ * mvtv_launch_log_read writes the log as text, one launch per line in launch order,
+ *   "<kernel name with template arguments>\t<grid x y z>\t<block x y z>\n",
+ * NUL-terminated and cut to cap bytes, and returns the length of the whole text (call with cap = 0 to size it). */
+void mvtv_launch_log_enable(int32_t on);
+int64_t mvtv_launch_log_read(char* buf, int64_t cap);
+
 #ifdef __cplusplus
 }
 #endif

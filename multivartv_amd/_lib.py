@@ -6,6 +6,7 @@ device is missing, every entry point raises.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 import os
@@ -101,6 +102,8 @@ SIGNATURES = {
     "mvtv_timing_enable": (C.c_int, [C.c_void_p, C.c_int32]),
     "mvtv_timing_get": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.POINTER(C.c_int64), _dp]),
     "mvtv_kernel_name": (C.c_char_p, [C.c_int32]),
+    "mvtv_launch_log_enable": (None, [C.c_int32]),
+    "mvtv_launch_log_read": (C.c_int64, [C.c_char_p, C.c_int64]),
 }
 
 
@@ -383,6 +386,29 @@ class Problem:
             _check(lib().mvtv_timing_get(self._h, k, C.byref(ms), C.byref(n), C.byref(b)))
             out[name] = dict(ms=ms.value, launches=n.value, bytes_per_launch=b.value)
         return out
+
+
+@contextlib.contextmanager
+def launch_log():
+    """Record the kernel launches this thread makes inside the ``with`` block: yields a list that holds one
+    ``(name, grid, block)`` per launch, in launch order, once the block is left (name with its template arguments,
+    e.g. ``k_trir<10, 32, 32>``; grid and block as 3-tuples)."""
+    L = lib()
+    out = []
+    L.mvtv_launch_log_enable(1)
+    try:
+        yield out
+    finally:
+        n = int(L.mvtv_launch_log_read(None, 0))
+        buf = C.create_string_buffer(n + 1)
+        L.mvtv_launch_log_read(buf, n + 1)
+        L.mvtv_launch_log_enable(0)
+        for line in buf.value.decode().splitlines():
+            if line.startswith("#"):   # the ring overflowed: "# <n> earlier launches dropped"
+                out.append((line, (0, 0, 0), (0, 0, 0)))
+                continue
+            name, grid, block = line.split("\t")
+            out.append((name, tuple(int(v) for v in grid.split()), tuple(int(v) for v in block.split())))
 
 
 def nan():

@@ -8,6 +8,8 @@
 //   C  code/solvers.py:53-76                          (mbs_one's loop)
 // Per ADMM iteration the host reads back 7 scalars (one stream sync); the PCG theta-solve
 // keeps its scalars on the device and is polled every few iterations.
+#include <cxxabi.h>
+#include <dlfcn.h>
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,6 +20,7 @@
 #include <complex>
 #include <cstdint>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -34,6 +37,42 @@ thread_local std::string g_last_error;
 namespace {
 
 int popcount(int x) { return __builtin_popcount(unsigned(x)); }
+
+// Readable name of a kernel from its host function pointer (the launch log): the runtime's registered device symbol,
+// else the host stub's own symbol, demangled and cut down to the name with its template arguments, e.g.
+// "k_trir<10, 32, 32>" from "void mvtv::k_trir<10, 32, 32>(double*, ...)".
+std::string kernel_display_name(const void* fn) {
+    const char* sym = hipKernelNameRefByPtr(fn, nullptr);
+    Dl_info info;
+    if (!sym || !*sym) {
+        (void)hipGetLastError();   // the failed lookup's error only: a pending launch error stays for its caller
+        if (dladdr(fn, &info) && info.dli_sname) sym = info.dli_sname;
+    }
+    if (!sym || !*sym) {
+        char p[32];
+        std::snprintf(p, sizeof p, "%p", fn);
+        return p;
+    }
+    int status = 0;
+    char* dem = abi::__cxa_demangle(sym, nullptr, nullptr, &status);
+    std::string s = (status == 0 && dem) ? dem : sym;
+    std::free(dem);
+    // the parameter list starts at the first '(' outside template brackets; the name at the last space before it
+    int depth = 0;
+    size_t start = 0, end = s.size();
+    for (size_t i = 0; i < s.size(); ++i) {
+        const char c = s[i];
+        if (c == '<') ++depth;
+        else if (c == '>') --depth;
+        else if (depth == 0 && c == ' ') start = i + 1;
+        else if (depth == 0 && c == '(' && s.compare(i, 21, "(anonymous namespace)") == 0) i += 20;
+        else if (depth == 0 && c == '(') { end = i; break; }
+    }
+    s = s.substr(start, end - start);
+    for (const char* prefix : {"mvtv::", "__device_stub__"})
+        if (s.compare(0, std::strlen(prefix), prefix) == 0) s.erase(0, std::strlen(prefix));
+    return s;
+}
 
 // Placement-aware z ping-pong: the fused 3-D kernel's time depends on WHICH physical
 // edge buffer it reads z from and writes to (profiles/r01/v12_zflip_probe.txt: up to 4.70 against
@@ -1974,6 +2013,42 @@ const char* mvtv_kernel_name(int32_t kid) {
                                                "dct_first", "dct", "admm_fused", "gather4_b", "dct_first_fold",
                                                "admm_fused4"};
     return (kid >= 0 && kid < MVTV_K_COUNT) ? names[kid] : "?";
+}
+
+void mvtv_launch_log_enable(int32_t on) {
+    // the ring's owner: freed here on disable, or at thread exit if the thread ends with the log on (g_launch_log
+    // itself stays trivially destructible, so klaunch's flag test needs no thread-local init guard)
+    static thread_local std::unique_ptr<LaunchRec[]> ring;
+    LaunchLog& L = g_launch_log;
+    L.on = false;
+    L.count = 0;
+    if (on && !ring) ring.reset(new LaunchRec[kLaunchLogCap]);
+    if (!on) ring.reset();
+    L.ring = ring.get();
+    L.on = on != 0;
+}
+
+int64_t mvtv_launch_log_read(char* buf, int64_t cap) {
+    const LaunchLog& L = g_launch_log;
+    std::string out;
+    if (L.ring) {
+        const uint64_t first = L.count > kLaunchLogCap ? L.count - kLaunchLogCap : 0;
+        if (first) out += "# " + std::to_string(first) + " earlier launches dropped\n";
+        for (uint64_t i = first; i < L.count; ++i) {
+            const LaunchRec& r = L.ring[i % kLaunchLogCap];
+            out += kernel_display_name(r.fn);
+            char dims[128];
+            std::snprintf(dims, sizeof dims, "\t%u %u %u\t%u %u %u\n", r.grid[0], r.grid[1], r.grid[2], r.block[0],
+                          r.block[1], r.block[2]);
+            out += dims;
+        }
+    }
+    if (buf && cap > 0) {
+        const size_t n = std::min(out.size(), size_t(cap - 1));
+        std::memcpy(buf, out.data(), n);
+        buf[n] = '\0';
+    }
+    return int64_t(out.size());
 }
 
 }  // extern "C"

@@ -199,8 +199,25 @@ struct TimedLaunch {
 extern thread_local TimedLaunch g_timed;
 extern thread_local TimedLaunch g_timed_b;   // a two-kernel launcher's second launch
 
+// Launch log (mvtv_launch_log_enable / mvtv_launch_log_read, for the tests): while the calling thread has it on,
+// klaunch records each kernel's host function pointer, grid and block in a ring of the last kLaunchLogCap
+// launches. Names are resolved when the log is read; off, a launch pays for one thread-local flag test.
+struct LaunchRec {
+    const void* fn;
+    uint32_t grid[3], block[3];
+};
+constexpr uint32_t kLaunchLogCap = 8192;
+struct LaunchLog {
+    bool on = false;
+    uint64_t count = 0;          // launches since enable; entry i lives at ring[i % kLaunchLogCap]
+    LaunchRec* ring = nullptr;   // kLaunchLogCap entries while on
+};
+extern thread_local LaunchLog g_launch_log;
+void launch_log_push(const void* fn, dim3 grid, dim3 block);
+
 template <typename F, typename... Args>
 inline void klaunch(F kernel, dim3 grid, dim3 block, uint32_t shmem, hipStream_t s, Args... args) {
+    if (g_launch_log.on) launch_log_push(reinterpret_cast<const void*>(kernel), grid, block);
     if (g_timed.start) {
         const TimedLaunch t = g_timed;
         g_timed = TimedLaunch{};

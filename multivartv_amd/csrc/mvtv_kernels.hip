@@ -20,6 +20,16 @@ namespace mvtv {
 
 thread_local TimedLaunch g_timed;
 thread_local TimedLaunch g_timed_b;
+thread_local LaunchLog g_launch_log;
+
+void launch_log_push(const void* fn, dim3 grid, dim3 block) {
+    LaunchLog& L = g_launch_log;
+    if (!L.ring) return;
+    LaunchRec& r = L.ring[L.count++ % kLaunchLogCap];
+    r.fn = fn;
+    r.grid[0] = grid.x, r.grid[1] = grid.y, r.grid[2] = grid.z;
+    r.block[0] = block.x, r.block[1] = block.y, r.block[2] = block.z;
+}
 
 // Jacobi diagonal of W + sigma * sum_S cS[S] (x)_{j in S} L_j at a node with multi-index c:
 // the 1-D Neumann Laplacian's diagonal is (c > 0) + (c < m - 1).

@@ -70,6 +70,18 @@ def test_host_only_calls():
     assert [L.mvtv_kernel_name(k).decode() for k in range(len(_lib.KERNELS))] == _lib.KERNELS
 
 
+def test_launch_log_is_empty_without_launches():
+    """The launch log's enable / read / disable calls are host-only: a block that launches nothing yields an empty
+    list, the text form is sized by a call without a buffer, and reading a disabled log gives nothing."""
+    L = mv.lib()
+    with _lib.launch_log() as log:
+        assert L.mvtv_launch_log_read(None, 0) == 0
+    assert log == []
+    assert L.mvtv_launch_log_read(None, 0) == 0
+    buf = ctypes.create_string_buffer(b"x", 4)
+    assert L.mvtv_launch_log_read(buf, 4) == 0 and buf.value == b""
+
+
 def test_no_device_fails_loudly():
     if mv.device_count() > 0:
         pytest.skip("a GPU is visible")
