@@ -132,6 +132,14 @@ mvtv_status mvtv_problem_block_info(const mvtv_problem* prob, int32_t k, int32_t
 mvtv_status mvtv_problem_set_data(mvtv_problem* prob, const double* oty, const double* wdiag);
 /* 1 if MVTV_SOLVER_SPECTRAL applies to this problem (W = I, every m_j <= 4096), else 0 */
 int32_t mvtv_problem_spectral_ok(const mvtv_problem* prob);
+/* The marching line sweeps of the 3-D spectral solve (m_1 = 512, m_0 a multiple of 16, one GPU): the dim-1 transforms
+ * fused into the dim-2 line solve, two passes over the vector and an interface step over `chunks` chunks of dim 2 in
+ * place of three passes. mode -1: automatic (the default: meshes of more than 2^24 nodes that fill the GPU with
+ * chunks of >= 8 planes), 0: off, 1: on wherever the shape admits it (any size; other shapes keep the five-pass solve).
+ * chunks 0: chosen by the library's cost model; mode 1 accepts 1 <= chunks <= min(m_2, 64). Waits for the problem's
+ * stream; (re)allocates 4 * chunks * m_0 * m_1 doubles of scratch. The environment variable MVTV_LINE_SWEEP=0, read
+ * when a problem is created, starts it in mode 0. */
+mvtv_status mvtv_problem_line_sweep(mvtv_problem* prob, int32_t mode, int32_t chunks);
 
 /* ---- the hot path ------------------------------------------------------------------ */
 /* Drop-in for admm_update:

@@ -82,6 +82,7 @@ SIGNATURES = {
     "mvtv_problem_block_info": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp]),
     "mvtv_problem_set_data": (C.c_int, [C.c_void_p, _dp, _dp]),
     "mvtv_problem_spectral_ok": (C.c_int32, [C.c_void_p]),
+    "mvtv_problem_line_sweep": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "mvtv_admm": (C.c_int, [C.c_void_p, C.POINTER(AdmmOpts), C.c_double, _dp, _dp, _dp, C.POINTER(AdmmStats)]),
     "mvtv_state_set": (C.c_int, [C.c_void_p, _dp, _dp, C.c_double]),
     "mvtv_state_get": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
@@ -368,6 +369,11 @@ class Problem:
 
     def spectral_ok(self) -> bool:
         return bool(lib().mvtv_problem_spectral_ok(self._h))
+
+    def line_sweep(self, mode=-1, chunks=0):
+        """The marching line sweeps of the 3-D spectral solve: -1 automatic, 0 off, 1 on wherever the shape admits
+        it; chunks 0 = the library's choice (mvtv_problem_line_sweep)."""
+        _check(lib().mvtv_problem_line_sweep(self._h, int(mode), int(chunks)))
 
     def solve_spectral(self, sigma, b):
         bb = _f64(b, self.N)

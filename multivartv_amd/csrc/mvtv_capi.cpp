@@ -174,7 +174,7 @@ mvtv_status pick_zpair(mvtv_problem* P, bool track_theta, bool twin) {
 void free_all(mvtv_problem* P) {
     double** bufs[] = {&P->oty, &P->wdiag, &P->theta, &P->edges, &P->ga, &P->gu, &P->guprev, &P->r,
                        &P->p, &P->q, &P->thold, &P->p2, &P->partials, &P->red, &P->stage, &P->slab_iface,
-                       &P->edges2, &P->pcg_b, &P->g4, &P->edges3, &P->pcg_s, &P->pcg_t};
+                       &P->edges2, &P->pcg_b, &P->g4, &P->edges3, &P->pcg_s, &P->pcg_t, &P->ls_coef, &P->ls_lr};
     for (double** b : bufs)
         if (*b) {
             (void)hipFree(*b);
@@ -494,6 +494,51 @@ mvtv_status spectral_plan(mvtv_problem* P) {
     return MVTV_OK;
 }
 
+// The marching line sweeps of a 3-D solve (mvtv_spectral.hip k_sweep): which problems take them, with how many chunks
+// over dim 2, and their scratch. mode -1: the gate (not a slab rank, N > 2^24 nodes, a grid of >= one workgroup per CU
+// with chunks of >= 8 planes); 1: wherever the shape has an instantiation; 0: off. chunks 0: the cost model's count.
+mvtv_status line_sweep_setup(mvtv_problem* P, int mode, int chunks) {
+    if (mode < -1 || mode > 1 || chunks < 0 || chunks > kLineSweepMaxChunks)
+        return fail(MVTV_BAD_ARG, "line_sweep: mode in {-1, 0, 1}, 0 <= chunks <= 64");
+    int C = 0;
+    if (mode != 0 && !P->slab && P->spec_mesh && line_sweep_shape_ok(P->g)) {
+        if (mode == 1) {
+            if (chunks > int(P->g.m[2])) return fail(MVTV_BAD_ARG, "line_sweep: more chunks than planes");
+            C = chunks > 0 ? chunks : line_sweep_chunks(P->g, false);
+        } else if (uint64_t(P->g.N) > (uint64_t(1) << 24)) {
+            C = line_sweep_chunks(P->g, true);
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(P->stream));   // no launch may still read the scratch
+    if (C > P->ls_cap) {
+        for (double** b : {&P->ls_coef, &P->ls_lr})
+            if (*b) {
+                (void)hipFree(*b);
+                *b = nullptr;
+            }
+        P->ls_cap = 0;
+        P->ls_chunks = 0;
+        const size_t words = 2 * size_t(C) * P->g.m[0] * P->g.m[1];
+        MVTV_TRY(alloc(&P->ls_coef, words));
+        MVTV_TRY(alloc(&P->ls_lr, words));
+        P->ls_cap = C;
+    }
+    P->ls_mode = mode;
+    P->ls_chunks = C;
+    return MVTV_OK;
+}
+
+// down sweep, interface, up sweep, in place on x (the dim-0 coefficients of the right-hand side, then of the solve)
+mvtv_status line_sweeps(mvtv_problem* P, double* x, double sigma, double w0, const AdmmCtl* ctl, const int32_t* skip) {
+    for (int phase = 0; phase < 3; ++phase) {
+        const int h = P->tstart(phase == 1 ? MVTV_K_REDUCE : MVTV_K_DCT);
+        HIP_TRY(launch_line_sweep(P->spec, P->g, P->stream, phase, x, P->ls_coef, P->ls_lr, P->ls_chunks, sigma, w0, ctl,
+                                  skip));
+        P->tstop(h);
+    }
+    return MVTV_OK;
+}
+
 // Direct solve (I + sigma D^T D) x = oty + ca*ga + cb*gb: forward DCT along dims 0..p-2, the
 // last dim's forward/divide/inverse in one pass, inverse DCT along dims p-2..0. All in place on x.
 // fold: b = oty + fold_ka ga + fold_kb gb from the control block (ga = the fused kernel's folded
@@ -531,6 +576,27 @@ mvtv_status spectral_solve(mvtv_problem* P, double sigma, const double* oty, con
         P->tstop(h);
         h = P->tstart(MVTV_K_DCT);
         HIP_TRY(launch_dct_pass(P->spec, P->g, P->stream, 1, 2, x, nullptr, 0.0, nullptr, 0.0, x, sigma, w0, ctl, 0, 0.0,
+                                skip));
+        P->tstop(h);
+        return MVTV_OK;
+    }
+    // 3-D, m1 = 512: dim-0 forward (b formed on load), the down sweep, the chunk interface, the up sweep, dim-0
+    // inverse: 9N words and the chunks' carries instead of 11N (line_sweep_setup chose ls_chunks)
+    if (!P->slab && P->ls_chunks > 0 && mid == p - 1) {
+        int h = P->tstart(ga ? (fold ? MVTV_K_DCT_FOLD : MVTV_K_DCT_FIRST) : MVTV_K_DCT);
+        if (ga && fold)
+            HIP_TRY(launch_dct_pass(P->spec, P->g, P->stream, 0, 0, oty, ga, 1.0, gb, 0.0, x, sigma, w0, ctl, 0, 0.0, skip,
+                                    nullptr, true));
+        else if (ga)
+            HIP_TRY(launch_dct_pass(P->spec, P->g, P->stream, 0, 0, oty, ga, ca, gb ? gb : ga, gb ? cb : 0.0, x, sigma, w0,
+                                    ctl, 0, 0.0, skip));
+        else
+            HIP_TRY(launch_dct_pass(P->spec, P->g, P->stream, 0, 0, oty, nullptr, 0.0, nullptr, 0.0, x, sigma, w0, ctl, 0,
+                                    0.0, skip));
+        P->tstop(h);
+        MVTV_TRY(line_sweeps(P, x, sigma, w0, ctl, skip));
+        h = P->tstart(MVTV_K_DCT);
+        HIP_TRY(launch_dct_pass(P->spec, P->g, P->stream, 1, 0, x, nullptr, 0.0, nullptr, 0.0, x, sigma, w0, ctl, 0, 0.0,
                                 skip));
         P->tstop(h);
         return MVTV_OK;
@@ -638,6 +704,10 @@ mvtv_status pcgs_solve(mvtv_problem* P, double sigma, const double* oty, const d
         for (int t = 0; t < 2 * pdim - 1; ++t) {
             const int d = t < pdim ? t : 2 * pdim - 2 - t;
             const int mode = t < pdim - 1 ? 0 : (t == pdim - 1 ? 2 : 1);
+            if (P->ls_chunks > 0 && t >= 1 && t <= 3) {   // the sweeps in place of the three middle passes
+                if (t == 1) MVTV_TRY(line_sweeps(P, z, sigma, w0, nullptr, skip));
+                continue;
+            }
             PcgFuse f;
             if (t == 0 || t == 2 * pdim - 2) {
                 f.mode = t == 0 ? 1 : 2;
@@ -905,6 +975,10 @@ mvtv_status problem_create_impl(const mvtv_problem_desc* d, const mvtv_slab_desc
     // a slab problem's last dimension is solved by the substructured line solves (any length): the tables
     // are needed for the transforms along dims 0..p-2 only
     if (P->spec_mesh || (P->slab && P->spec_lead && p >= 2)) s = spectral_plan(P);
+    if (s == MVTV_OK && P->spec_mesh && !P->slab) {   // the marching line sweeps: the gate, MVTV_LINE_SWEEP=0 off
+        const char* e = std::getenv("MVTV_LINE_SWEEP");
+        s = line_sweep_setup(P, (e && std::atoi(e) == 0) ? 0 : -1, 0);
+    }
     P->e3d = edge3d_ok(g);
     if (s == MVTV_OK && P->e3d && g.p == 4 && gather4_ok(g)) s = alloc(&P->g4, 4 * size_t(N));
     P->f3d = fused3d_ok(g);   // slab problems too: the fused pass runs on the owned planes (Geom.ibeg/iend)
@@ -954,6 +1028,12 @@ int64_t mvtv_problem_nodes(const mvtv_problem* P) { return P ? int64_t(P->g.N) :
 int64_t mvtv_problem_edges(const mvtv_problem* P) { return P ? P->E : 0; }
 int32_t mvtv_problem_blocks(const mvtv_problem* P) { return P ? P->g.nb : 0; }
 int32_t mvtv_problem_spectral_ok(const mvtv_problem* P) { return P && spectral_ok(P) ? 1 : 0; }
+
+mvtv_status mvtv_problem_line_sweep(mvtv_problem* P, int32_t mode, int32_t chunks) {
+    if (!P) return fail(MVTV_BAD_ARG, "null problem");
+    DeviceGuard dg(P->device);
+    return line_sweep_setup(P, mode, chunks);
+}
 
 mvtv_status mvtv_problem_block_info(const mvtv_problem* P, int32_t k, int32_t* code, int32_t* sprime, double* weight) {
     if (!P || k < 0 || k >= P->g.nb) return fail(MVTV_BAD_ARG, "block index");
@@ -1290,7 +1370,8 @@ mvtv_status mvtv_admm_run(mvtv_problem* P, const mvtv_admm_opts* opts_in, double
                                                   reinterpret_cast<const void*>(uintptr_t(fold)),
                                                   reinterpret_cast<const void*>(uintptr_t(track_theta)),
                                                   reinterpret_cast<const void*>(uintptr_t(fused)),
-                                                  reinterpret_cast<const void*>(uintptr_t(twin))};
+                                                  reinterpret_cast<const void*>(uintptr_t(twin)), P->ls_coef,
+                                                  reinterpret_cast<const void*>(uintptr_t(P->ls_chunks))};
             auto it = std::find_if(P->graphs.begin(), P->graphs.end(), [&](const auto& lg) { return lg.key == key; });
             if (it == P->graphs.end()) {
                 // capture iterations 1 and 2; any failure leaves stream launches for this key (best effort)

@@ -20,7 +20,8 @@ namespace mvtv {
 // Experiment knobs (tile shapes, buffer placement probes, alternative kernels) are read from the
 // environment only in a probe build (`make PROBES=1`, -DMVTV_PROBES); the release library always
 // takes the defaults. The run-time options a user may set are MVTV_ZPICK=0 (keep the allocation-order
-// z buffer pair), MVTV_ADMM_SYNC=1 (host-synchronous ADMM loop) and MVTV_PCG=classic (3-kernel PCG).
+// z buffer pair), MVTV_LINE_SWEEP=0 (the 3-D solve's marching line sweeps off), MVTV_ADMM_SYNC=1
+// (host-synchronous ADMM loop) and MVTV_PCG=classic (3-kernel PCG).
 inline const char* probe_env(const char* name) {
 #ifdef MVTV_PROBES
     return std::getenv(name);
@@ -344,6 +345,17 @@ bool march_ok(const Geom& g);
 // forward elimination along dim 1) or backward (back substitution + inverse dim-0 DCT, scaled by m1 / N)
 hipError_t launch_march(const SpecPlan& sp, const Geom& g, hipStream_t s, bool bwd, double* x, double sigma, double w0,
                         const AdmmCtl* ctl = nullptr, const int32_t* skip = nullptr);
+// The dim-1 transforms and the dim-2 line solve of a 3-D mesh as two marching sweeps with the chunk interface between
+// them (k_sweep, k_trisr_iface): dim-0 forward pass, down sweep, interface, up sweep, dim-0 inverse pass. Shapes:
+// p = 3, m1 = 512, m0 a multiple of 16. line_sweep_chunks: the cost model's chunk count over dim 2 (<= m2,
+// <= kLineSweepMaxChunks); gate = true returns 0 unless some grid has >= one workgroup per CU with chunks of >= 8
+// planes. launch_line_sweep: phase 0 down, 1 interface, 2 up, in place on x; coef and lr hold 2 C m0 m1 doubles each.
+constexpr int kLineSweepMaxChunks = 64;
+bool line_sweep_shape_ok(const Geom& g);
+int line_sweep_chunks(const Geom& g, bool gate);
+hipError_t launch_line_sweep(const SpecPlan& sp, const Geom& g, hipStream_t s, int phase, double* x, double* coef,
+                             double* lr, int C, double sigma, double w0, const AdmmCtl* ctl = nullptr,
+                             const int32_t* skip = nullptr);
 // true when the d = 0 passes of this mesh run in k_dct8 with their partial rows within partial_words
 bool dct_pcg_fusable(const Geom& g, size_t partial_words);
 // radices (8, 4, 2, 3, 5, 7 in stage order) of a line length m = 2^a 3^b 5^c 7^d; false for any other m

@@ -98,6 +98,11 @@ struct mvtv_problem {
     double wsum_own = 0.0, wsum2_own = 0.0;   // sum W, sum W^2 over the nodes [ibeg, iend) (slab: owned planes)
     double* pcg_s = nullptr;      // 1/s of the scaled spectral preconditioner
     double* pcg_t = nullptr;      // r / s, the preconditioner's input
+    // the marching line sweeps of the 3-D spectral solve (k_sweep; mvtv_problem_line_sweep)
+    int ls_mode = -1;             // -1 auto (the gate), 0 off, 1 on wherever the shape admits it
+    int ls_chunks = 0;            // chunks over dim 2 in use; 0: the five-pass solve
+    double *ls_coef = nullptr, *ls_lr = nullptr;   // the chunks' pairs and carries, ls_cap chunks each
+    int ls_cap = 0;
     AdmmCtl* ctl = nullptr;       // device control block of the asynchronous ADMM loop
     AdmmCtl* host_ctl = nullptr;  // pinned mirror
     int admm_hint = 0;            // ADMM iterations of the last converged run (enqueue-ahead depth)

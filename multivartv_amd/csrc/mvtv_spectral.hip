@@ -3551,6 +3551,264 @@ __global__ __launch_bounds__(256) void k_trisr_iface(const SpecArgs a, const dou
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// k_sweep: the dim-1 transforms of a 3-D solve fused into the dim-2 line solve as two marching sweeps (round 7).
+// The factorised line solve is two first-order recursions with one constant r per (k0, k1) line, so a workgroup that
+// owns a k_dct8 strided tile (16 adjacent k0 x all m1 = 2^L points of dim 1) and marches the planes of dim 2 keeps its
+// 16 coefficients per thread, (k1, M - k1) pairs x 2 adjacent k0, in the same registers from plane to plane:
+//   down (UP = false), i = hi - 1 ... lo: dim-1 forward DCT of the plane's tile (k_dct8's strided forward pass), then
+//       B <- f + r B from B = 0 and Fs <- Fs + p f, p <- p r from p = 1; B is stored in the pass's coefficient layout,
+//       and (Fs, B) at the chunk's end go to coef as k_trisr<1> writes them: F at the chunk's last row and B at its
+//       first row, each from a zero carry;
+//   (k_trisr_iface over the C chunks as "ranks": the true F entering every chunk's first row, B entering its last)
+//   up (UP = true), i = lo ... hi - 1: with the stored B_i and B_{i+1} (0 past the chunk's top) f_i = B_i - r B_{i+1}
+//       (k_trisr<3>'s recovery: the carry's terms cancel in it), x_i = (scale / D) (B_i + r^(hi-i) Bin + r F),
+//       F <- r F + f_i from F = Fin, then k_dct8's strided inverse pass on x_i.
+// The planes of dim 2 split into C chunks [floor(m2 k / C), floor(m2 (k + 1) / C)) (k_trisr_iface's block rule);
+// workgroup b owns tile b % (m0 / 16) of chunk b / (m0 / 16). In place: a chunk reads and writes its own planes only,
+// plane i + 1 is read before it is written. The three launches are ordered by the stream alone.
+// r^(hi-i) by binary powering per step (the exponent is uniform over the workgroup): no division by r (r = 0 at
+// sigma = 0), and a factor that underflows belongs to a term below the result's rounding.
+// Registers: B, Fs, p (down) or r, F, Bin (up) and two planes' values, 16 doubles each; r (down) or scale / D (up) and
+// the twiddles sit in LDS beside the exchange buffer, so the loop holds no invariant loads the compiler could hoist
+// into registers (224 / 235 VGPRs, no scratch, 153 KB of LDS). One 512-thread workgroup per CU (L = 9). Barriers in
+// the plane loop order LDS only, so the next plane's loads, issued before this plane's stages, stay in flight. The
+// down sweep keeps p as a running product: powering it per plane as the up sweep must cost 577 against 449 us.
+template <int L, bool UP>
+__global__ __launch_bounds__((spec8::Shape<L>::NT)) void k_sweep(const SpecArgs a, double* __restrict__ car,
+                                                                  uint32_t m2, int C) {
+    using S = spec8::Shape<L>;
+    constexpr int M = S::M, TPL = S::TPL, NCL = S::NCL, NT = S::NT, R0 = S::R0;
+    static_assert(S::TQ == 16 && L >= 6, "k_sweep: 16-line tiles (m1 <= 512)");
+    double sigma = a.sigma;
+    if (a.skip && *a.skip) return;
+    if (a.ctl) {
+        if (a.ctl->done) return;
+        sigma = a.ctl->sigma;
+    }
+    __shared__ double2 buf[NCL * S::LP];          // FFT exchange (k_dct8's slot layout)
+    __shared__ double2 s_tw[M], s_twq[M];         // radix-8 stages index tw up to 7 M / 8
+    __shared__ double s_lc[16 * NT];              // this thread's 16 line constants [e][t]: r (down), scale / D (up)
+    const int t = threadIdx.x;
+    const int j0 = t / NCL, c0 = t % NCL;
+    const uint32_t m0 = a.m[0];
+    const uint32_t ntile = m0 / 16u;
+    const uint32_t tile = blockIdx.x % ntile, ck = blockIdx.x / ntile;
+    const uint32_t lo = uint32_t(uint64_t(m2) * ck / uint32_t(C)), hi = uint32_t(uint64_t(m2) * (ck + 1u) / uint32_t(C));
+    const size_t ps = size_t(m0) * M;             // plane
+    const size_t nl = ps;                         // lines
+
+    for (int i = t; i < M; i += NT) {
+        s_twq[i] = a.twq[i];
+        s_tw[i] = a.tw[i];
+    }
+
+    // line constants of the coefficients e = 4 s + {0, 1}: (ka, k0 | k0 + 1), {2, 3}: (kb, k0 | k0 + 1), as k_trisr
+    // builds them
+    double r[UP ? 16 : 1];
+    {
+        const uint32_t k0 = tile * 16u + uint32_t(2 * c0);
+        const double l0[2] = {a.lam[a.lam_off[0] + k0], a.lam[a.lam_off[0] + k0 + 1u]};
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int k = j0 + s * TPL;
+            const int kk[2] = {k, k ? M - k : M / 2};
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const double l1 = a.lam[a.lam_off[1] + uint32_t(kk[h])];
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    double c0v = a.w0, c1v = 0.0;
+                    for (int Sm = 1; Sm < 8; ++Sm) {
+                        if (a.cS[Sm] == 0.0) continue;
+                        double prod = sigma * a.cS[Sm];
+                        if (Sm & 1) prod *= l0[e];
+                        if (Sm & 2) prod *= l1;
+                        if (Sm & 4) c1v += prod;
+                        else c0v += prod;
+                    }
+                    const double D = sqrt(c0v * (c0v + 4.0 * c1v));
+                    const double den = 1.0 / (c0v + 2.0 * c1v + D);
+                    if constexpr (UP) {
+                        r[4 * s + 2 * h + e] = 2.0 * c1v * den;
+                        s_lc[(4 * s + 2 * h + e) * NT + t] = a.inv_n * double(m2) / D;
+                    } else {
+                        s_lc[(4 * s + 2 * h + e) * NT + t] = 2.0 * c1v * den;
+                    }
+                }
+            }
+        }
+    }
+    // [chunk][2][line]: the pair (k0, k0 + 1) of coefficient (s, h)
+    auto carp = [&](int which, int s, int h) -> double* {
+        const int k = j0 + s * TPL;
+        const uint32_t k1 = uint32_t(h == 0 ? k : (k ? M - k : M / 2));
+        return car + (size_t(ck) * 2 + size_t(which)) * nl + size_t(k1) * m0 + (tile * 16u + uint32_t(2 * c0));
+    };
+    // y r^n by binary powering (n is uniform over the workgroup)
+    auto rpow = [](double rp, uint32_t n, double y) -> double {
+        for (; n; n >>= 1) {
+            if (n & 1u) y *= rp;
+            rp *= rp;
+        }
+        return y;
+    };
+    __syncthreads();   // the tables
+
+    // The plane loops take the thread's coordinates through an opaque copy per iteration: the indices derived from
+    // them (8 LDS slots per exchange, 8 global offsets) are then recomputed per plane, a few integer operations,
+    // where the compiler would otherwise keep them all in registers over the loop, next to the 16-element state
+#define MVTV_SWEEP_COORDS                                            \
+    int j = j0, c = c0;                                              \
+    asm volatile("" : "+v"(j), "+v"(c));                             \
+    double2* const X = buf + c * S::LP;                              \
+    const int cx = c & 7;                                            \
+    const uint32_t k0 = tile * 16u + uint32_t(2 * c)
+
+    if constexpr (!UP) {
+        double B[16], Fs[16], pw[16];
+#pragma unroll
+        for (int e = 0; e < 16; ++e) B[e] = 0.0, Fs[e] = 0.0, pw[e] = 1.0;
+        double2 zn[8];
+        auto issue = [&](uint32_t i, int j, uint32_t k0) {
+            const double* p = a.in + size_t(i) * ps + k0;
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const int n = stage_in_pos<L, R0>(j, q);
+                const uint32_t k = n < M / 2 ? uint32_t(2 * n) : uint32_t(2 * (M - 1 - n) + 1);
+                zn[q] = ldnt2(p + k * m0);
+            }
+        };
+        issue(hi - 1u, j0, tile * 16u + uint32_t(2 * c0));
+        for (uint32_t i = hi; i-- > lo;) {
+            MVTV_SWEEP_COORDS;
+            double2 z[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) z[q] = zn[q];
+            if (i > lo) issue(i - 1u, j, k0);
+            stages_from<L, R0, 1, false, false, 1>(z, j, X, cx, s_tw);   // natural-order spectrum in LDS
+            double* const o = a.out + size_t(i) * ps + k0;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const int k = j + s * TPL;
+                const int ka = k, kb = k ? M - k : M / 2;
+                const double2 Z1 = X[spec8::slot(ka, cx)], Z2 = X[spec8::slot(kb, cx)];
+                const double2 q1 = s_twq[ka], q2 = s_twq[kb];
+                double2 Xk, Xmk;
+                if (k == 0) {
+                    Xk = make_double2(q1.x * Z1.x, q1.x * Z1.y);
+                    Xmk = make_double2(q2.x * Z2.x, q2.x * Z2.y);
+                } else {
+                    const double2 Ap = make_double2(0.5 * (Z1.x + Z2.x), 0.5 * (Z1.y - Z2.y));
+                    const double2 Bp = make_double2(0.5 * (Z1.y + Z2.y), -0.5 * (Z1.x - Z2.x));
+                    Xk = make_double2(q1.x * Ap.x - q1.y * Ap.y, q1.x * Bp.x - q1.y * Bp.y);
+                    Xmk = make_double2(q2.x * Ap.x + q2.y * Ap.y, q2.x * Bp.x + q2.y * Bp.y);
+                }
+                const double f[4] = {Xk.x, Xk.y, Xmk.x, Xmk.y};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int x = 4 * s + e;
+                    const double rx = s_lc[x * NT + t];
+                    B[x] = fma(rx, B[x], f[e]);
+                    Fs[x] = fma(pw[x], f[e], Fs[x]);   // r^(hi-1-i) f_i
+                    pw[x] *= rx;
+                }
+                stnt2(o + uint32_t(ka) * m0, make_double2(B[4 * s], B[4 * s + 1]));
+                stnt2(o + uint32_t(kb) * m0, make_double2(B[4 * s + 2], B[4 * s + 3]));
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int x = 4 * s + 2 * h;
+                stnt2(carp(0, s, h), make_double2(Fs[x], Fs[x + 1]));
+                stnt2(carp(1, s, h), make_double2(B[x], B[x + 1]));
+            }
+    } else {
+        double F[16], Bin[16], cur[16], nxt[16];
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int x = 4 * s + 2 * h;
+                const double2 fv = ldnt2(carp(0, s, h)), bv = ldnt2(carp(1, s, h));
+                F[x] = fv.x;
+                F[x + 1] = fv.y;
+                Bin[x] = bv.x;
+                Bin[x + 1] = bv.y;
+            }
+        auto issue = [&](uint32_t i, double* v, int j, uint32_t k0) {   // plane i's stored B; zero past the chunk's top
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const int k = j + s * TPL;
+                const int ka = k, kb = k ? M - k : M / 2;
+                double2 va = make_double2(0.0, 0.0), vb = va;
+                if (i < hi) {
+                    const double* p = a.in + size_t(i) * ps + k0;
+                    va = ldnt2(p + uint32_t(ka) * m0);
+                    vb = ldnt2(p + uint32_t(kb) * m0);
+                }
+                v[4 * s] = va.x;
+                v[4 * s + 1] = va.y;
+                v[4 * s + 2] = vb.x;
+                v[4 * s + 3] = vb.y;
+            }
+        };
+        issue(lo, cur, j0, tile * 16u + uint32_t(2 * c0));
+        issue(lo + 1u, nxt, j0, tile * 16u + uint32_t(2 * c0));
+        for (uint32_t i = lo; i < hi; ++i) {
+            MVTV_SWEEP_COORDS;
+            const uint32_t n = hi - i;
+            xbar<1>();   // the last stage of plane i - 1 has read its inputs
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                double xv[4];
+#pragma unroll
+                for (int e4 = 0; e4 < 4; ++e4) {
+                    const int e = 4 * s + e4;
+                    const double f = fma(-r[e], nxt[e], cur[e]);
+                    xv[e4] = s_lc[e * NT + t] * (cur[e] + rpow(r[e], n, Bin[e]) + r[e] * F[e]);
+                    F[e] = fma(r[e], F[e], f);
+                    cur[e] = nxt[e];
+                }
+                const int k = j + s * TPL;
+                const int ka = k, kb = k ? M - k : M / 2;
+                const double2 Xk = make_double2(xv[0], xv[1]), Xmk = make_double2(xv[2], xv[3]);
+                const double2 q1 = cconj(s_twq[ka]), q2 = cconj(s_twq[kb]);
+                if (k == 0) {
+                    const double2 va2 = cmul(q2, make_double2(Xmk.x, -Xmk.x));
+                    const double2 vb2 = cmul(q2, make_double2(Xmk.y, -Xmk.y));
+                    X[spec8::slot(0, cx)] = Xk;
+                    X[spec8::slot(M / 2, cx)] = make_double2(va2.x - vb2.y, va2.y + vb2.x);
+                } else {
+                    const double2 va1 = cmul(q1, make_double2(Xk.x, -Xmk.x));
+                    const double2 vb1 = cmul(q1, make_double2(Xk.y, -Xmk.y));
+                    const double2 va2 = cmul(q2, make_double2(Xmk.x, -Xk.x));
+                    const double2 vb2 = cmul(q2, make_double2(Xmk.y, -Xk.y));
+                    X[spec8::slot(ka, cx)] = make_double2(va1.x - vb1.y, va1.y + vb1.x);
+                    X[spec8::slot(kb, cx)] = make_double2(va2.x - vb2.y, va2.y + vb2.x);
+                }
+            }
+            issue(i + 2u, nxt, j, k0);   // in flight over the stages and the stores of plane i (plane i + 2: not written yet)
+            xbar<1>();
+            double2 z[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) z[q] = X[spec8::slot(stage_in_pos<L, R0>(j, q), cx)];
+            stages_from<L, R0, 1, true, true, 1>(z, j, X, cx, s_tw);
+            using LS = LastStage<L>;
+            double* const o = a.out + size_t(i) * ps + k0;
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const int nn = stage_out_pos<L, LS::R, LS::NS>(j, q);
+                const uint32_t k = nn < M / 2 ? uint32_t(2 * nn) : uint32_t(2 * (M - 1 - nn) + 1);
+                stnt2(o + k * m0, z[q]);
+            }
+        }
+    }
+#undef MVTV_SWEEP_COORDS
+}
+
 static void tris_seg(uint32_t n, int* sl, int* nseg) {
     // >= 4 segments when the block allows it, segments of <= 16 rows (32 past 1024 rows), <= 64 segments
     uint32_t s = std::max<uint32_t>(1u, std::min<uint32_t>(n > 1024u ? 32u : 16u, n / 4u));
@@ -4110,6 +4368,81 @@ hipError_t launch_march(const SpecPlan& sp, const Geom& g, hipStream_t s, bool b
         default: return hipErrorInvalidValue;
     }
 #undef MVTV_MARCH
+    return hipGetLastError();
+}
+
+// The marching line sweeps (k_sweep): shapes with an instantiation
+bool line_sweep_shape_ok(const Geom& g) {
+    return g.p == 3 && g.m[1] == 512u && g.m[0] % 16u == 0u && g.m[2] >= 2u;
+}
+
+// Chunk count of the sweeps: the grid runs in rounds of the resident workgroups (occupancy x CUs), and a round lasts
+// as long as its longest chunk, plus the chunk's share of fixed work in plane steps: the line constants and the
+// pipeline's fill (~1) and the carries (8 words per line and chunk over the two sweeps and the interface, against the
+// 4 a plane step moves: 2). Ties take the fewer chunks. 0: no grid of >= one workgroup per CU with chunks of >= 8
+// planes (the auto gate). 512^3: 32 tiles x 8 chunks of 64 planes, one round of one workgroup a CU.
+int line_sweep_chunks(const Geom& g, bool gate) {
+    if (!line_sweep_shape_ok(g)) return 0;
+    static thread_local int dev = -1, slots = 256, cus = 256;
+    int dv = 0;
+    if (hipGetDevice(&dv) == hipSuccess && dv != dev) {
+        hipDeviceProp_t prop;
+        int per_cu = 1;
+        cus = 256;
+        if (hipGetDeviceProperties(&prop, dv) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_sweep<9, true>, spec8::Shape<9>::NT, 0) != hipSuccess ||
+            per_cu < 1) {
+            (void)hipGetLastError();
+            per_cu = 1;
+        }
+        slots = per_cu * cus;
+        dev = dv;
+    }
+    const uint32_t ntile = g.m[0] / 16u, m2 = g.m[2];
+    int best = 0;
+    uint64_t best_cost = ~uint64_t(0);
+    for (uint32_t C = 1; C <= std::min<uint32_t>(m2, uint32_t(kLineSweepMaxChunks)); ++C) {
+        if (gate && (ntile * C < uint32_t(cus) || m2 / C < 8u)) continue;
+        const uint64_t rounds = (uint64_t(ntile) * C + uint32_t(slots) - 1) / uint32_t(slots);
+        const uint64_t cost = rounds * ((m2 + C - 1) / C + 3u);
+        if (cost < best_cost) best_cost = cost, best = int(C);
+    }
+    return best;
+}
+
+// phase 0: the down sweep (x holds the dim-0 coefficients; writes B and the chunks' pairs to coef), 1: the interface
+// (coef -> lr), 2: the up sweep (reads lr; x = the solve's dim-0 coefficients). coef, lr: 2 C m0 m1 doubles each.
+hipError_t launch_line_sweep(const SpecPlan& sp, const Geom& g, hipStream_t s, int phase, double* x, double* coef,
+                             double* lr, int C, double sigma, double w0, const AdmmCtl* ctl, const int32_t* skip) {
+    if (!line_sweep_shape_ok(g) || C < 1 || uint32_t(C) > g.m[2] || !x || !coef || !lr) return hipErrorInvalidValue;
+    const uint32_t nl = g.m[0] * g.m[1];
+    if (phase < 0 || phase > 2) return hipErrorInvalidValue;
+    SpecArgs a{};
+    a.ctl = ctl;
+    a.skip = skip;
+    a.in = x;
+    a.out = x;
+    a.tw = reinterpret_cast<const double2*>(sp.tw + sp.tw_off[1]);
+    a.twq = reinterpret_cast<const double2*>(sp.twq + sp.twq_off[1]);
+    a.lam = sp.lam;
+    for (int j = 0; j < kMaxDims; ++j) {
+        a.lam_off[j] = sp.lam_off[j];
+        a.m[j] = g.m[j];
+    }
+    for (int S = 0; S < 16; ++S) a.cS[S] = g.cS[S];
+    a.sigma = sigma;
+    a.w0 = w0;
+    a.inv_n = 1.0 / double(g.N);
+    a.d = 2;
+    a.p = 3;
+    for (int j = 0; j < kMaxDims - 1; ++j) a.fd[j] = g.fd[j];
+    if (phase == 1) {   // the chunks as k_trisr_iface's ranks: every line owned here (rank 0 of chunk m0 m1)
+        klaunch(k_trisr_iface, dim3((nl + 255u) / 256u), dim3(256), 0, s, a, coef, lr, nl, C, 0, g.m[2]);
+        return hipGetLastError();
+    }
+    const dim3 grid(g.m[0] / 16u * uint32_t(C)), block(spec8::Shape<9>::NT);
+    if (phase == 0) klaunch(k_sweep<9, false>, grid, block, 0, s, a, coef, g.m[2], C);
+    else klaunch(k_sweep<9, true>, grid, block, 0, s, a, lr, g.m[2], C);
     return hipGetLastError();
 }
 
