@@ -103,6 +103,19 @@ def apply_D(m, theta, deltas, order=0, weighted=1):
     return d
 
 
+def apply_Dt(m, v, deltas, order=0, weighted=1):
+    L = _bind_ext()
+    mm, dl = _geom_args(m, deltas)
+    vv = np.ascontiguousarray(v, dtype=np.float64)
+    if vv.size != num_edges(m, order, weighted):
+        raise ValueError(f"expected {num_edges(m, order, weighted)} edge values, got {vv.size}")
+    out = np.empty(int(np.prod([int(x) for x in m])))
+    if L.mvtv_oracle_apply_Dt(len(m), mm, order, weighted, dl.ctypes.data_as(_dp), vv.ctypes.data_as(_dp),
+                              out.ctypes.data_as(_dp)) != 0:
+        raise RuntimeError("apply_Dt")
+    return out
+
+
 def dtd_symbol(m, deltas, order=0, weighted=1):
     """sum_S cS[S] prod_{j in S} 4 sin^2(pi k_j / 2 m_j) on the (k_0, ..., k_{p-1}) grid (Fortran order):
     the eigenvalues of D^T D in the cosine basis (cS[S] = sum of w_b^2 over blocks with S'(b) = S)."""
