@@ -88,8 +88,10 @@ typedef enum mvtv_theta_solver {
     MVTV_SOLVER_AUTO = 0,      /* SPECTRAL where it is exact; else PCG_SPECTRAL on the same meshes; else PCG */
     MVTV_SOLVER_PCG = 1,       /* Jacobi-PCG on the 3^p-point stencil, warm-started, pcg_rtol */
     MVTV_SOLVER_SPECTRAL = 2,  /* direct: cosine transforms + a tridiagonal solve along the last dim. Exact for
-                                  W = I (mesh == data) with every m_j <= 4096 (FFT plans for lengths with prime
-                                  factors 2, 3, 5, 7, Bluestein's chirp-z for any other); MVTV_BAD_ARG otherwise */
+                                  W = I (mesh == data) with m_j <= 4096 for j < p - 1 (FFT plans for lengths with
+                                  prime factors 2, 3, 5, 7, Bluestein's chirp-z for any other) and a last dimension
+                                  of any length (never transformed: a line solve, in blocks past 4096 rows);
+                                  MVTV_BAD_ARG otherwise */
     MVTV_SOLVER_PCG_SPECTRAL = 3 /* PCG preconditioned by S (mean(W) I + sigma D^T D) S, its middle factor inverted
                                   exactly by cosine transforms, S = I or a Jacobi-like diagonal scaling when W varies
                                   strongly against sigma D^T D's diagonal: for W != I (scattered data, CV folds) on
@@ -130,8 +132,18 @@ int32_t mvtv_problem_blocks(const mvtv_problem* prob);
 mvtv_status mvtv_problem_block_info(const mvtv_problem* prob, int32_t k, int32_t* code, int32_t* sprime, double* weight);
 /* new O^T y and W for the same mesh (CV folds re-run create_cache_objects, rcpp…/solvers.cpp:347-348) */
 mvtv_status mvtv_problem_set_data(mvtv_problem* prob, const double* oty, const double* wdiag);
-/* 1 if MVTV_SOLVER_SPECTRAL applies to this problem (W = I, every m_j <= 4096), else 0 */
+/* 1 if MVTV_SOLVER_SPECTRAL applies to this problem (W = I, m_j <= 4096 for j < p - 1; the last dimension any length
+ * on one GPU), else 0 */
 int32_t mvtv_problem_spectral_ok(const mvtv_problem* prob);
+/* The line solve along the last dimension in `blocks` blocks [floor(m k / blocks), floor(m (k + 1) / blocks)) of every
+ * line: per-block recursion sums, an interface step that gives every block its carries and closes the mirror, and a
+ * rerun from the carries (three launches, 3N words instead of the 2N of a line that fits one workgroup). blocks 0:
+ * automatic (the default): the one-workgroup kernels where m_last <= 4096, the library's block count beyond. blocks
+ * >= 2: that many blocks at any m_last (tests; an A/B against the one-workgroup kernels; the marching line sweeps
+ * rest meanwhile). MVTV_BAD_ARG for blocks < 0, 1, > m_last, a block longer than a workgroup takes (4096 rows at
+ * p = 1; 1024 at p >= 2, 2048 with fewer than 16 lines), a slab rank, or a mesh the spectral solve does not accept. Waits for the problem's stream;
+ * (re)allocates 4 * blocks * N / m_last doubles of scratch. */
+mvtv_status mvtv_problem_line_blocks(mvtv_problem* prob, int32_t blocks);
 /* The marching line sweeps of the 3-D spectral solve (m_1 = 512, m_0 a multiple of 16, one GPU): the dim-1 transforms
  * fused into the dim-2 line solve, two passes over the vector and an interface step over `chunks` chunks of dim 2 in
  * place of three passes. mode -1: automatic (the default: meshes of more than 2^24 nodes that fill the GPU with

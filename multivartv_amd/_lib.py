@@ -83,6 +83,7 @@ SIGNATURES = {
     "mvtv_problem_set_data": (C.c_int, [C.c_void_p, _dp, _dp]),
     "mvtv_problem_spectral_ok": (C.c_int32, [C.c_void_p]),
     "mvtv_problem_line_sweep": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "mvtv_problem_line_blocks": (C.c_int, [C.c_void_p, C.c_int32]),
     "mvtv_admm": (C.c_int, [C.c_void_p, C.POINTER(AdmmOpts), C.c_double, _dp, _dp, _dp, C.POINTER(AdmmStats)]),
     "mvtv_state_set": (C.c_int, [C.c_void_p, _dp, _dp, C.c_double]),
     "mvtv_state_get": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
@@ -374,6 +375,11 @@ class Problem:
         """The marching line sweeps of the 3-D spectral solve: -1 automatic, 0 off, 1 on wherever the shape admits
         it; chunks 0 = the library's choice (mvtv_problem_line_sweep)."""
         _check(lib().mvtv_problem_line_sweep(self._h, int(mode), int(chunks)))
+
+    def line_blocks(self, blocks=0):
+        """The line solve along the last dimension in blocks: 0 automatic (only where m_last > 4096), >= 2 that many
+        blocks at any m_last (mvtv_problem_line_blocks)."""
+        _check(lib().mvtv_problem_line_blocks(self._h, int(blocks)))
 
     def solve_spectral(self, sigma, b):
         bb = _f64(b, self.N)

@@ -183,7 +183,7 @@ void free_all(mvtv_problem* P) {
     if (P->st) (void)hipFree(P->st);
     if (P->ctl) (void)hipFree(P->ctl);
     if (P->host_ctl) (void)hipHostFree(P->host_ctl);
-    for (double* t : {P->spec.tw, P->spec.twq, P->spec.lam, P->spec.blu})
+    for (double* t : {P->spec.tw, P->spec.twq, P->spec.lam, P->spec.blu, P->spec.lb_coef, P->spec.lb_lr})
         if (t) (void)hipFree(t);
     if (P->spec.perm) (void)hipFree(P->spec.perm);
     P->spec = SpecPlan{};
@@ -438,6 +438,8 @@ mvtv_status spectral_plan(mvtv_problem* P) {
         sp.tw_off[j] = uint32_t(tw.size());
         sp.twq_off[j] = uint32_t(twq.size());
         sp.lam_off[j] = uint32_t(lam.size());
+        // a last dimension longer than 4096 is never transformed (the blocked line solve reads no table of it)
+        if (P->spec_long && j == P->g.p - 1) continue;
         for (uint32_t k = 0; k < m; ++k) {
             const long double a = -2.0L * pi * k / m;
             tw.push_back(double(cosl(a)));
@@ -486,6 +488,12 @@ mvtv_status spectral_plan(mvtv_problem* P) {
         return MVTV_OK;
     };
     if (!blu.empty()) MVTV_TRY(up(&sp.blu, blu));
+    if (tw.empty()) {   // p = 1 with a long line: no table at all; the passes still take the pointers
+        tw.assign(2, 0.0);
+        twq.assign(2, 0.0);
+        lam.assign(1, 0.0);
+        perm.assign(1, 0u);
+    }
     MVTV_TRY(up(&sp.tw, tw));
     MVTV_TRY(up(&sp.twq, twq));
     MVTV_TRY(up(&sp.lam, lam));
@@ -501,7 +509,7 @@ mvtv_status line_sweep_setup(mvtv_problem* P, int mode, int chunks) {
     if (mode < -1 || mode > 1 || chunks < 0 || chunks > kLineSweepMaxChunks)
         return fail(MVTV_BAD_ARG, "line_sweep: mode in {-1, 0, 1}, 0 <= chunks <= 64");
     int C = 0;
-    if (mode != 0 && !P->slab && P->spec_mesh && line_sweep_shape_ok(P->g)) {
+    if (mode != 0 && !P->slab && P->spec_mesh && !P->spec_long && line_sweep_shape_ok(P->g)) {
         if (mode == 1) {
             if (chunks > int(P->g.m[2])) return fail(MVTV_BAD_ARG, "line_sweep: more chunks than planes");
             C = chunks > 0 ? chunks : line_sweep_chunks(P->g, false);
@@ -527,6 +535,39 @@ mvtv_status line_sweep_setup(mvtv_problem* P, int mode, int chunks) {
     P->ls_chunks = C;
     return MVTV_OK;
 }
+
+// The blocked line solve along the last dimension (mvtv_spectral.hip k_trib / k_tri1): blocks 0: only where the last
+// dimension is longer than 4096, with the library's block count; >= 2: that many blocks at any length. The blocks'
+// pairs and carries live in the plan, allocated here when the solve is in use.
+mvtv_status line_blocks_setup(mvtv_problem* P, int blocks) {
+    if (P->slab || !P->spec_mesh)
+        return fail(MVTV_BAD_ARG, "line_blocks: not a slab rank, and m_j <= 4096 for j < p - 1");
+    const uint32_t mlast = P->g.m[P->g.p - 1];
+    if (blocks < 0 || blocks == 1 || uint32_t(blocks) > mlast)
+        return fail(MVTV_BAD_ARG, "line_blocks: 0 or 2 <= blocks <= m_last");
+    LineBlocks lb;
+    if ((blocks > 0 || P->spec_long) && !line_blocks_plan(P->g, blocks, &lb))
+        return fail(MVTV_BAD_ARG, "line_blocks: a block of the last dimension does not fit a workgroup's segments");
+    HIP_TRY(hipStreamSynchronize(P->stream));   // no launch may still read the scratch
+    SpecPlan& sp = P->spec;
+    const size_t words = 2 * size_t(lb.nblk) * size_t(P->g.N / mlast);
+    if (words > sp.lb_cap) {
+        for (double** b : {&sp.lb_coef, &sp.lb_lr})
+            if (*b) {
+                (void)hipFree(*b);
+                *b = nullptr;
+            }
+        sp.lb_cap = 0;
+        sp.lb = LineBlocks{};
+        MVTV_TRY(alloc(&sp.lb_coef, words));
+        MVTV_TRY(alloc(&sp.lb_lr, words));
+        sp.lb_cap = words;
+    }
+    sp.lb = lb;   // (forced blocks on a line-sweep mesh: the five-pass solve while they are on, sweeps_on)
+    return MVTV_OK;
+}
+
+bool sweeps_on(const mvtv_problem* P) { return P->ls_chunks > 0 && P->spec.lb.nblk == 0; }
 
 // down sweep, interface, up sweep, in place on x (the dim-0 coefficients of the right-hand side, then of the solve)
 mvtv_status line_sweeps(mvtv_problem* P, double* x, double sigma, double w0, const AdmmCtl* ctl, const int32_t* skip) {
@@ -582,7 +623,7 @@ mvtv_status spectral_solve(mvtv_problem* P, double sigma, const double* oty, con
     }
     // 3-D, m1 = 512: dim-0 forward (b formed on load), the down sweep, the chunk interface, the up sweep, dim-0
     // inverse: 9N words and the chunks' carries instead of 11N (line_sweep_setup chose ls_chunks)
-    if (!P->slab && P->ls_chunks > 0 && mid == p - 1) {
+    if (!P->slab && sweeps_on(P) && mid == p - 1) {
         int h = P->tstart(ga ? (fold ? MVTV_K_DCT_FOLD : MVTV_K_DCT_FIRST) : MVTV_K_DCT);
         if (ga && fold)
             HIP_TRY(launch_dct_pass(P->spec, P->g, P->stream, 0, 0, oty, ga, 1.0, gb, 0.0, x, sigma, w0, ctl, 0, 0.0, skip,
@@ -704,7 +745,7 @@ mvtv_status pcgs_solve(mvtv_problem* P, double sigma, const double* oty, const d
         for (int t = 0; t < 2 * pdim - 1; ++t) {
             const int d = t < pdim ? t : 2 * pdim - 2 - t;
             const int mode = t < pdim - 1 ? 0 : (t == pdim - 1 ? 2 : 1);
-            if (P->ls_chunks > 0 && t >= 1 && t <= 3) {   // the sweeps in place of the three middle passes
+            if (sweeps_on(P) && t >= 1 && t <= 3) {   // the sweeps in place of the three middle passes
                 if (t == 1) MVTV_TRY(line_sweeps(P, z, sigma, w0, nullptr, skip));
                 continue;
             }
@@ -961,17 +1002,22 @@ mvtv_status problem_create_impl(const mvtv_problem_desc* d, const mvtv_slab_desc
         return s;
     }
     P->host_st = reinterpret_cast<PcgState*>(P->host_red + 16);
-    // cosine transforms of any length <= 4096: FFT plans for 2-3-5-7 lengths, Bluestein (k_dctb) for the rest
+    // cosine transforms of any length <= 4096: FFT plans for 2-3-5-7 lengths, Bluestein (k_dctb) for the rest. The last
+    // dimension is never transformed: on one GPU it may have any length (spec_long: the blocked line solve); a slab
+    // rank keeps the old rule (its loop has the substructured solve over the ranks)
     P->spec_mesh = P->spec_pow2 = P->spec_lead = true;
+    P->spec_long = false;
     for (int j = 0; j < p; ++j) {
         const uint32_t mj = uint32_t(mg[j]);
         if (mj > 4096) {
-            P->spec_mesh = false;
             if (j < p - 1) P->spec_lead = false;
+            if (j == p - 1 && !P->slab) P->spec_long = true;
+            else P->spec_mesh = false;
         }
         if ((mj & (mj - 1)) != 0) P->spec_pow2 = false;
     }
-    if (!P->spec_mesh) P->spec_pow2 = false;
+    if (!P->spec_mesh) P->spec_long = false;
+    if (!P->spec_mesh || P->spec_long) P->spec_pow2 = false;
     // a slab problem's last dimension is solved by the substructured line solves (any length): the tables
     // are needed for the transforms along dims 0..p-2 only
     if (P->spec_mesh || (P->slab && P->spec_lead && p >= 2)) s = spectral_plan(P);
@@ -979,6 +1025,7 @@ mvtv_status problem_create_impl(const mvtv_problem_desc* d, const mvtv_slab_desc
         const char* e = std::getenv("MVTV_LINE_SWEEP");
         s = line_sweep_setup(P, (e && std::atoi(e) == 0) ? 0 : -1, 0);
     }
+    if (s == MVTV_OK && P->spec_long) s = line_blocks_setup(P, 0);
     P->e3d = edge3d_ok(g);
     if (s == MVTV_OK && P->e3d && g.p == 4 && gather4_ok(g)) s = alloc(&P->g4, 4 * size_t(N));
     P->f3d = fused3d_ok(g);   // slab problems too: the fused pass runs on the owned planes (Geom.ibeg/iend)
@@ -1033,6 +1080,12 @@ mvtv_status mvtv_problem_line_sweep(mvtv_problem* P, int32_t mode, int32_t chunk
     if (!P) return fail(MVTV_BAD_ARG, "null problem");
     DeviceGuard dg(P->device);
     return line_sweep_setup(P, mode, chunks);
+}
+
+mvtv_status mvtv_problem_line_blocks(mvtv_problem* P, int32_t blocks) {
+    if (!P) return fail(MVTV_BAD_ARG, "null problem");
+    DeviceGuard dg(P->device);
+    return line_blocks_setup(P, blocks);
 }
 
 mvtv_status mvtv_problem_block_info(const mvtv_problem* P, int32_t k, int32_t* code, int32_t* sprime, double* weight) {
@@ -1135,9 +1188,9 @@ mvtv_status mvtv_admm_run(mvtv_problem* P, const mvtv_admm_opts* opts_in, double
     if (o.theta_solver < MVTV_SOLVER_AUTO || o.theta_solver > MVTV_SOLVER_PCG_SPECTRAL)
         return fail(MVTV_BAD_ARG, "theta_solver");
     if (o.theta_solver == MVTV_SOLVER_SPECTRAL && !spectral_ok(P))
-        return fail(MVTV_BAD_ARG, "spectral theta-solve needs W = I and every m_j <= 4096");
+        return fail(MVTV_BAD_ARG, "spectral theta-solve needs W = I and m_j <= 4096 for j < p - 1");
     if (o.theta_solver == MVTV_SOLVER_PCG_SPECTRAL && (!P->spec_mesh || P->wmode == W_NONE))
-        return fail(MVTV_BAD_ARG, "spectral preconditioner needs every m_j <= 4096");
+        return fail(MVTV_BAD_ARG, "spectral preconditioner needs m_j <= 4096 for j < p - 1");
     const bool spectral = o.theta_solver == MVTV_SOLVER_SPECTRAL ||
                           (o.theta_solver == MVTV_SOLVER_AUTO && spectral_ok(P));
     // AUTO with W != I on a spectral mesh: PCG with the spectral preconditioner (K an order of magnitude
@@ -1371,7 +1424,8 @@ mvtv_status mvtv_admm_run(mvtv_problem* P, const mvtv_admm_opts* opts_in, double
                                                   reinterpret_cast<const void*>(uintptr_t(track_theta)),
                                                   reinterpret_cast<const void*>(uintptr_t(fused)),
                                                   reinterpret_cast<const void*>(uintptr_t(twin)), P->ls_coef,
-                                                  reinterpret_cast<const void*>(uintptr_t(P->ls_chunks))};
+                                                  reinterpret_cast<const void*>(uintptr_t(P->ls_chunks)), P->spec.lb_coef,
+                                                  reinterpret_cast<const void*>(uintptr_t(P->spec.lb.nblk))};
             auto it = std::find_if(P->graphs.begin(), P->graphs.end(), [&](const auto& lg) { return lg.key == key; });
             if (it == P->graphs.end()) {
                 // capture iterations 1 and 2; any failure leaves stream launches for this key (best effort)
@@ -2003,7 +2057,7 @@ mvtv_status mvtv_lambda_max_cpp(mvtv_problem* P, double* out, int32_t* iters) {
 
 mvtv_status mvtv_solve_spectral(mvtv_problem* P, double sigma, const double* b, double* x_out) {
     if (!P || !b || !x_out) return fail(MVTV_BAD_ARG, "null argument");
-    if (!spectral_ok(P)) return fail(MVTV_BAD_ARG, "spectral theta-solve needs W = I and every m_j <= 4096");
+    if (!spectral_ok(P)) return fail(MVTV_BAD_ARG, "spectral theta-solve needs W = I and m_j <= 4096 for j < p - 1");
     DeviceGuard dg(P->device);
     double* dx = nullptr;
     MVTV_TRY(alloc(&dx, P->g.N));

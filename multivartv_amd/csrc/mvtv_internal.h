@@ -303,8 +303,18 @@ hipError_t launch_edges_z_to_u(hipStream_t s, double* edges, uint64_t n, double 
 // edges = value on every real edge, 0 on padding (variant u0 fills: B 0, A and C 1/lambda)
 hipError_t launch_edges_fill_valid(const Geom& g, int order, const Launch& L, double* edges, double value);
 hipError_t launch_apply_D_padded(const Geom& g, int order, const Launch& L, const double* theta, double* edges);
+// The blocked line solve along the last dimension (k_trib, k_tri1): nblk blocks of the line by k_trisr_iface's rule;
+// p >= 2: tq lines per workgroup, nseg segments of sl rows (the last ones shorter or empty); p = 1: tq = 0
+struct LineBlocks {
+    int nblk = 0, tq = 0, sl = 0, nseg = 0;
+};
 // Spectral theta-solve tables (mvtv_spectral.hip), device-resident, offsets in doubles.
 struct SpecPlan {
+    // the blocked last-dimension solve (lb.nblk > 0: SPEC_MID along d = p - 1 takes it): the blocks' pairs and
+    // carries, [block][2][line] each, lb_cap doubles
+    LineBlocks lb;
+    double *lb_coef = nullptr, *lb_lr = nullptr;
+    size_t lb_cap = 0;
     double* tw = nullptr;     // per dim: m_j complex FFT twiddles e^{-2 pi i k/m_j}
     double* twq = nullptr;    // per dim: m_j complex twiddles e^{-i pi k/(2 m_j)}
     double* lam = nullptr;    // per dim: m_j eigenvalues 4 sin^2(pi k/(2 m_j)) of the Neumann Laplacian
@@ -356,12 +366,16 @@ int line_sweep_chunks(const Geom& g, bool gate);
 hipError_t launch_line_sweep(const SpecPlan& sp, const Geom& g, hipStream_t s, int phase, double* x, double* coef,
                              double* lr, int C, double sigma, double w0, const AdmmCtl* ctl = nullptr,
                              const int32_t* skip = nullptr);
+// the blocked solve's shape for g's last dimension: blocks = 0 the library's count, >= 2 that many; false when
+// blocks > m_last or a block does not fit a workgroup's segments
+bool line_blocks_plan(const Geom& g, int blocks, LineBlocks* lb);
 // true when the d = 0 passes of this mesh run in k_dct8 with their partial rows within partial_words
 bool dct_pcg_fusable(const Geom& g, size_t partial_words);
 // radices (8, 4, 2, 3, 5, 7 in stage order) of a line length m = 2^a 3^b 5^c 7^d; false for any other m
 bool dct_radix_plan(uint32_t m, int* rad, int* nrad);
 // mode 0 forward DCT-II, 1 inverse (DCT-III, unnormalised), 2 forward + divide by mu * N + inverse;
-// ga != nullptr forms the input as in + ca*ga + cb*gb. In place (in == out) is allowed.
+// ga != nullptr forms the input as in + ca*ga + cb*gb. In place (in == out) is allowed. m_d <= 4096, except mode 2
+// along d = p - 1 while sp.lb.nblk > 0: the blocked line solve (three launches; p = 1: 16-B aligned arrays).
 hipError_t launch_dct_pass(const SpecPlan& sp, const Geom& g, hipStream_t s, int mode, int d, const double* in,
                            const double* ga, double ca, const double* gb, double cb, double* out, double sigma,
                            double w0, const AdmmCtl* ctl = nullptr, uint32_t q_off = 0, double inv_n = 0.0,

@@ -79,7 +79,8 @@ struct mvtv_problem {
     double* host_red = nullptr;   // pinned: reductions + PcgState mirror
     PcgState* host_st = nullptr;
     SpecPlan spec;                // spectral theta-solve tables (allocated when the mesh allows it)
-    bool spec_mesh = false;       // every m_j <= 4096 a product of 2, 3, 5, 7 (spectral solve)
+    bool spec_mesh = false;       // spectral solve: m_j <= 4096 for j < p - 1; the last dimension too on a slab rank
+    bool spec_long = false;       // ... with a last dimension longer than 4096 (the blocked line solve, spec.lb)
     bool spec_pow2 = false;       // ... and a power of two (k_dct8 / k_tri passes)
     bool spec_lead = false;       // dims 0..p-2 are (the slab loop: the last dimension may have any length)
     bool e3d = false;             // z-marching 3-D edge kernels

@@ -809,7 +809,7 @@ mvtv_status slab_run(mvtv_problem* P, mvtv_comm* C, const mvtv_admm_opts* opts, 
     if (opts->variant != MVTV_VARIANT_RCPP) return fail(MVTV_BAD_ARG, "the slab loop runs variant B");
     if (P->wmode == W_NONE || !P->spec_lead || P->g.p < 2)
         return fail(MVTV_BAD_ARG, "slab loop: W = I or diagonal, p >= 2, m_j <= 4096 for j < p - 1");
-    if (C->size == 1 && !P->spec_mesh)
+    if (C->size == 1 && (!P->spec_mesh || P->spec_long))
         return fail(MVTV_BAD_ARG, "slab loop on one rank: the last dimension too must be <= 4096");
     if (!(lambda >= 0.0) || !(rho0 > 0.0)) return fail(MVTV_BAD_ARG, "lambda >= 0 and rho0 > 0");
     const auto t0 = std::chrono::steady_clock::now();

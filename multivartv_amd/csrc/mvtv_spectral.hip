@@ -3552,6 +3552,479 @@ __global__ __launch_bounds__(256) void k_trisr_iface(const SpecArgs a, const dou
 }
 
 // ---------------------------------------------------------------------------------------------
+// The last dimension of any length on one GPU: the same substructuring with the blocks of one line as the "ranks".
+// The line's m rows split into nblk blocks [floor(m k / nblk), floor(m (k + 1) / nblk)) (k_trisr_iface's rule: two
+// block lengths at most). Phase 1 runs every block's recursions from zero carries and leaves (F at its last row, B at
+// its first) in coef [block][2][line]; the interface turns them into every block's carries lr [block][2][line] and
+// closes the mirror; phase 3 reruns the block from its carries and writes the solve. Phase 1 only reads: 3N words and
+// 2 nblk nlines doubles each way per solve, against the 2N of a line that fits one workgroup.
+//
+// k_trib (p >= 2): k_trigr's tile (TQ adjacent lines x NS segments of sl <= SMAX rows) on a (line tile x block) grid,
+// tile fastest. A block of n rows has n / sl whole segments, one of n % sl rows and empty ones after it (the longer
+// block length sizes the workgroup); a segment's multiplier is r^rows, 1 for an empty one. d = p - 1: the line stride
+// is the plane, nlines of them, any count and any stride.
+//
+// Multipliers. A long line at a large sigma has r close to 1 in every line that matters (p = 1: c1 / c0 = sigma w^2 in
+// the one line there is), and the recursions' gain 1 / (1 - r) turns the half-ulp that rounding r to a double loses
+// into a relative 1e-16 / (1 - r) of the whole solve (4e-14 at c1 / c0 = 2e5: a systematic error of the constant
+// component, above the forward-error bound of the tests). So every multiplier here is a pair h + l: h = 1 - t rounded
+// and l = (1 - h) - t, exact where h >= 1/2, from the cancellation-free t = 1 - r^n; t_n comes from t alone
+// (t_{a+b} = t_a + t_b - t_a t_b: a few eps relative for any n), never from powers of the rounded r.
+namespace trib {
+constexpr int SMAX = 32;
+}
+
+__device__ __forceinline__ double tpow(double t, uint32_t n) {   // 1 - r^n from t = 1 - r
+    double y = 0.0, x = t;
+    while (n) {
+        if (n & 1u) y = fma(-y, x, y + x);
+        x = fma(-x, x, x + x);
+        n >>= 1;
+    }
+    return y;
+}
+struct Mul2 {
+    double h, l;
+};
+__device__ __forceinline__ Mul2 mul2_from_t(double t) {
+    const double h = 1.0 - t;
+    return {h, h >= 0.5 ? (1.0 - h) - t : 0.0};
+}
+__device__ __forceinline__ double mul2_mac(Mul2 m, double acc, double f) { return fma(m.h, acc, fma(m.l, acc, f)); }
+__device__ __forceinline__ Mul2 mul2_mul(Mul2 a, Mul2 b) {
+    const double h = a.h * b.h;
+    return {h, fma(a.h, b.h, -h) + fma(a.h, b.l, a.l * b.h)};
+}
+
+template <int PHASE, int SMAX, int TQ, int NS>
+__global__ __launch_bounds__((TQ * NS)) void k_trib(const SpecArgs a, int sl, uint32_t nblk, uint32_t ntile,
+                                                    double* __restrict__ coef, const double* __restrict__ lr) {
+    double sigma = a.sigma;
+    if (a.skip && *a.skip) return;
+    if (a.ctl) {
+        if (a.ctl->done) return;
+        sigma = a.ctl->sigma;
+    }
+    __shared__ double s_f[NS][TQ], s_b[NS][TQ];
+    __shared__ double s_rh[TQ], s_rl[TQ], s_sd[TQ];
+    const int t = threadIdx.x, c = t % TQ, sj = t / TQ;
+    const int nseg = int(blockDim.x) / TQ;
+    const uint32_t kb = blockIdx.x / ntile, tile = blockIdx.x - kb * ntile;
+    const uint32_t m = a.m[a.d];
+    const uint32_t lo = uint32_t(uint64_t(m) * kb / nblk), hi = uint32_t(uint64_t(m) * (kb + 1) / nblk);
+    const int n = int(hi - lo);
+    const int ln = min(max(n - sj * sl, 0), sl);   // this thread's segment length
+    const uint32_t q0 = tile * uint32_t(TQ);
+    const uint32_t q = q0 + uint32_t(c);
+    const bool valid = q < a.nlines;
+    const uint32_t qq = valid ? q : q0;
+    const size_t base = size_t(qq) + (size_t(lo) + size_t(sj * sl)) * a.stride;
+
+    double lamv[kMaxDims] = {0, 0, 0, 0};
+    if (t < TQ) {
+        uint32_t rest = a.q_off + qq;
+        for (int jj = 0; jj < a.p - 1; ++jj) {
+            const uint32_t qd = (jj < a.p - 2) ? a.fd[jj].div(rest) : 0u;
+            lamv[jj] = a.lam[a.lam_off[jj] + (rest - qd * a.m[jj])];
+            rest = qd;
+        }
+    }
+    double g[SMAX];
+    {
+        const double* pin = a.in + base;
+#pragma unroll
+        for (int i = 0; i < SMAX; ++i) {
+            g[i] = (valid && i < ln) ? __builtin_nontemporal_load(pin) : 0.0;
+            pin += a.stride;
+        }
+    }
+    const int nfull = n / sl, rem = n - nfull * sl;   // whole segments, the rows of the one after them
+    Mul2 rsl{0.0, 0.0}, rrem{1.0, 0.0};               // t < TQ: r^sl, r^rem
+    if (t < TQ) {
+        double c0 = a.w0, c1 = 0.0;
+        for (int Sm = 1; Sm < (1 << a.p); ++Sm) {
+            if (a.cS[Sm] == 0.0) continue;
+            double prod = sigma * a.cS[Sm];
+            for (int jj = 0; jj < a.p - 1; ++jj)
+                if ((Sm >> jj) & 1) prod *= lamv[jj];
+            if ((Sm >> (a.p - 1)) & 1) c1 += prod;
+            else c0 += prod;
+        }
+        const double D = sqrt(c0 * (c0 + 4.0 * c1));
+        const double den = 1.0 / (c0 + 2.0 * c1 + D);
+        const double t1 = (c0 + D) * den;   // 1 - r
+        rsl = mul2_from_t(tpow(t1, uint32_t(sl)));
+        rrem = mul2_from_t(tpow(t1, uint32_t(rem)));
+        const Mul2 r1 = mul2_from_t(t1);
+        s_rh[c] = r1.h;
+        s_rl[c] = r1.l;
+        s_sd[c] = a.inv_n * double(m) / D;
+    }
+    __syncthreads();
+
+    const Mul2 r{s_rh[c], s_rl[c]};
+    {
+        double fl = 0.0, bl = 0.0;
+#pragma unroll
+        for (int i = 0; i < SMAX; ++i) {
+            if (i < ln) fl = mul2_mac(r, fl, g[i]);
+            bl = mul2_mac(r, bl, g[SMAX - 1 - i]);   // rows past ln are 0
+        }
+        s_f[sj][c] = fl;
+        s_b[sj][c] = bl;
+    }
+    __syncthreads();
+
+    if (t < TQ) {
+        // phase 1: the block's F at its last row and B at its first row from zero carries; phase 3: every
+        // segment's carries from the block's
+        double acc = 0.0, bcc = 0.0;
+        if (PHASE == 3) {
+            acc = lr[(size_t(kb) * 2) * a.nlines + qq];
+            bcc = lr[(size_t(kb) * 2 + 1) * a.nlines + qq];
+        }
+        auto mult = [&](int k) { return k < nfull ? rsl : (k == nfull ? rrem : Mul2{1.0, 0.0}); };
+        for (int k = 0; k < nseg; ++k) {
+            const int kr = nseg - 1 - k;
+            const double fk = s_f[k][c], bk = s_b[kr][c];
+            if (PHASE == 3) {
+                s_f[k][c] = acc;
+                s_b[kr][c] = bcc;
+            }
+            acc = mul2_mac(mult(k), acc, fk);
+            bcc = mul2_mac(mult(kr), bcc, bk);
+        }
+        if (PHASE == 1 && valid) {
+            coef[(size_t(kb) * 2) * a.nlines + q] = acc;
+            coef[(size_t(kb) * 2 + 1) * a.nlines + q] = bcc;
+        }
+    }
+    if constexpr (PHASE == 3) {
+        __syncthreads();
+        if (!valid) return;
+        const double sd = s_sd[c], bin = s_b[sj][c];
+        double fv = s_f[sj][c];
+        {
+            double bv = bin;
+#pragma unroll
+            for (int i = SMAX - 1; i >= 0; --i)
+                if (i < ln) {
+                    bv = mul2_mac(r, bv, g[i]);
+                    g[i] = bv;
+                }
+        }
+        double* pout = a.out + base;
+#pragma unroll
+        for (int i = 0; i < SMAX; ++i)
+            if (i < ln) {
+                const double gn = i + 1 < ln ? g[i + 1] : bin;
+                __builtin_nontemporal_store(sd * mul2_mac(r, fv, g[i]), pout);
+                pout += a.stride;
+                fv = mul2_mac(r, fv - gn, g[i]);
+            }
+    }
+}
+
+// k_trib's interface: one thread per line walks the nblk blocks twice (k_trisr_iface's steps with the multipliers as
+// pairs): the line's totals from zero carries, the mirror closure, then every block's carries in order.
+__global__ __launch_bounds__(256) void k_trib_iface(const SpecArgs a, const double* __restrict__ co,
+                                                    double* __restrict__ lr, uint32_t nblk) {
+    double sigma = a.sigma;
+    if (a.skip && *a.skip) return;
+    if (a.ctl) {
+        if (a.ctl->done) return;
+        sigma = a.ctl->sigma;
+    }
+    const uint32_t l = blockIdx.x * blockDim.x + threadIdx.x;
+    if (l >= a.nlines) return;
+    const size_t C = a.nlines;
+    double lamv[kMaxDims] = {0, 0, 0, 0};
+    uint32_t rest = a.q_off + l;
+    for (int jj = 0; jj < a.p - 1; ++jj) {
+        const uint32_t qd = (jj < a.p - 2) ? a.fd[jj].div(rest) : 0u;
+        lamv[jj] = a.lam[a.lam_off[jj] + (rest - qd * a.m[jj])];
+        rest = qd;
+    }
+    double c0 = a.w0, c1 = 0.0;
+    for (int Sm = 1; Sm < (1 << a.p); ++Sm) {
+        if (a.cS[Sm] == 0.0) continue;
+        double prod = sigma * a.cS[Sm];
+        for (int jj = 0; jj < a.p - 1; ++jj)
+            if ((Sm >> jj) & 1) prod *= lamv[jj];
+        if ((Sm >> (a.p - 1)) & 1) c1 += prod;
+        else c0 += prod;
+    }
+    const double D = sqrt(c0 * (c0 + 4.0 * c1));
+    const double t1 = (c0 + D) / (c0 + 2.0 * c1 + D);
+    const uint32_t m = a.m[a.d], nlo = m / nblk;
+    const double tlo = tpow(t1, nlo);
+    const Mul2 mlo = mul2_from_t(tlo), mhi = mul2_from_t(fma(-tlo, t1, tlo + t1));
+    auto rblk = [&](uint32_t k) {
+        const uint32_t nk = uint32_t(uint64_t(m) * (k + 1) / nblk - uint64_t(m) * k / nblk);
+        return nk == nlo ? mlo : mhi;
+    };
+    double acc = 0.0, bcc = 0.0;
+    for (uint32_t k = 0; k < nblk; ++k) acc = mul2_mac(rblk(k), acc, co[(size_t(k) * 2) * C + l]);
+    for (uint32_t k = nblk; k > 0; --k) bcc = mul2_mac(rblk(k - 1), bcc, co[(size_t(k - 1) * 2 + 1) * C + l]);
+    const double tm = tpow(t1, m), pm = 1.0 - tm, idet = 1.0 / (tm * (2.0 - tm));   // r^m, 1 / (1 - r^2m)
+    double f = (bcc + pm * acc) * idet, b = (acc + pm * bcc) * idet;                // F_{-1} = B_0, B_m = F_{m-1}
+    for (uint32_t k = 0; k < nblk; ++k) {
+        lr[(size_t(k) * 2) * C + l] = f;
+        f = mul2_mac(rblk(k), f, co[(size_t(k) * 2) * C + l]);
+    }
+    for (uint32_t k = nblk; k > 0; --k) {
+        lr[(size_t(k - 1) * 2 + 1) * C + l] = b;
+        b = mul2_mac(rblk(k - 1), b, co[(size_t(k - 1) * 2 + 1) * C + l]);
+    }
+}
+
+// Exclusive weighted scan over the workgroup's threads in order (REV: from the last thread down). Every thread holds
+// v, the sum of its rows from a zero carry, and p, the multiplier r^rows of its span; (ev, ep) is what the threads
+// before it make of a zero carry and their multiplier, tv the whole workgroup's sum. Wave shuffles, then the NW waves'
+// pairs through LDS (s_v, s_h, s_l: NW doubles each). Every thread of the NW * 64 calls it.
+template <int NW, bool REV>
+__device__ __forceinline__ void wg_scan_pair(double v, Mul2 p, double* s_v, double* s_h, double* s_l, double& ev,
+                                             Mul2& ep, double& tv) {
+    const int lane = int(threadIdx.x) & 63, w = int(threadIdx.x) >> 6;
+    auto from = [&](double x, int off) { return REV ? __shfl_down(x, off) : __shfl_up(x, off); };
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const double lv = from(v, off);
+        const Mul2 lp{from(p.h, off), from(p.l, off)};
+        if (REV ? lane + off < 64 : lane >= off) {
+            v = mul2_mac(p, lv, v);
+            p = mul2_mul(p, lp);
+        }
+    }
+    if (lane == (REV ? 0 : 63)) {
+        s_v[w] = v;
+        s_h[w] = p.h;
+        s_l[w] = p.l;
+    }
+    double xv = from(v, 1);
+    Mul2 xp{from(p.h, 1), from(p.l, 1)};
+    if (lane == (REV ? 63 : 0)) {
+        xv = 0.0;
+        xp = Mul2{1.0, 0.0};
+    }
+    __syncthreads();
+    double wv = 0.0;
+    Mul2 wp{1.0, 0.0}, tp{1.0, 0.0};
+    tv = 0.0;
+#pragma unroll
+    for (int k = 0; k < NW; ++k) {
+        const int kk = REV ? NW - 1 - k : k;
+        if (kk == w) {
+            wv = tv;
+            wp = tp;
+        }
+        const Mul2 pk{s_h[kk], s_l[kk]};
+        tv = mul2_mac(pk, tv, s_v[kk]);
+        tp = mul2_mul(tp, pk);
+    }
+    ev = mul2_mac(xp, wv, xv);
+    ep = mul2_mul(wp, xp);
+    __syncthreads();
+}
+
+// k_tri1 (p = 1): one contiguous line, one constant r. A workgroup owns a block of <= NT * R rows; they move between
+// memory and LDS as coalesced 16-B accesses (the block's first and last rows, which may sit in a pair's other half,
+// and a line's odd last row singly), and thread t takes its R consecutive rows from LDS (pitch R + 1: the threads' rows
+// on different banks). The threads' pairs combine by the weighted scan with multiplier r^rows. FORMB (the ADMM loop's
+// only pass): phase 1 forms b = in + ca ga + cb gb on load and writes it to out, phase 3 reads it there: 6N words per
+// solve, against the 7N of forming it twice.
+namespace tri1 {
+constexpr int NT = 256, R = 16, BL = NT * R;   // threads, rows per thread, rows per block at most
+constexpr int NP = BL / 2 / NT + 1;            // 16-B pairs per thread over a block and its two edge pairs
+}
+
+template <int PHASE, bool FORMB>
+__global__ __launch_bounds__(tri1::NT) void k_tri1(const SpecArgs a, uint32_t nblk, double* __restrict__ coef,
+                                                   const double* __restrict__ lr) {
+    using namespace tri1;
+    double sigma = a.sigma, ca = a.ca, cb = a.cb;
+    if (a.skip && *a.skip) return;
+    if (a.ctl) {
+        if (a.ctl->done) return;
+        sigma = a.ctl->sigma;
+        ca = a.ctl->rho;
+        cb = a.ctl->rho * a.ctl->c_prev;
+    }
+    __shared__ double s_x[BL + NT];   // row i of the block at i + i / R
+    __shared__ double s_v[NT / 64], s_h[NT / 64], s_l[NT / 64];
+    const int t = threadIdx.x;
+    const uint32_t m = a.m[0], kb = blockIdx.x;
+    const uint32_t lo = uint32_t(uint64_t(m) * kb / nblk), hi = uint32_t(uint64_t(m) * (kb + 1) / nblk);
+    const int n = int(hi - lo);
+    const double* src = (FORMB && PHASE == 3) ? a.out : a.in;
+    const uint32_t e0 = (lo & ~1u) + 2u * uint32_t(t);   // this thread's first pair (16-B aligned)
+
+    // line constants (p = 1: c0 = w0, c1 = sigma cS[{0}])
+    const double c0 = a.w0, c1 = sigma * a.cS[1];
+    const double D = sqrt(c0 * (c0 + 4.0 * c1));
+    const double den = 1.0 / (c0 + 2.0 * c1 + D);
+    const double t1 = (c0 + D) * den, sd = a.inv_n * double(m) / D;   // 1 - r
+    const Mul2 r = mul2_from_t(t1);
+
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        const uint32_t e = e0 + uint32_t(2 * NT * j);
+        if (e >= hi) continue;
+        const bool in0 = e >= lo, in1 = e + 1u < hi;   // in1 implies e + 1 < m
+        double2 v;
+        if (in1) {
+            v = ldnt2(src + e);
+            if (FORMB && PHASE == 1) {
+                const double2 va = ldnt2(a.ga + e), vb = ldnt2(a.gb + e);
+                v.x += ca * va.x + cb * vb.x;
+                v.y += ca * va.y + cb * vb.y;
+            }
+        } else {
+            v.x = __builtin_nontemporal_load(src + e);
+            if (FORMB && PHASE == 1)
+                v.x += ca * __builtin_nontemporal_load(a.ga + e) + cb * __builtin_nontemporal_load(a.gb + e);
+            v.y = 0.0;
+        }
+        if (FORMB && PHASE == 1) {
+            if (in0 && in1) stnt2(a.out + e, v);
+            else if (in0) __builtin_nontemporal_store(v.x, a.out + e);
+            else __builtin_nontemporal_store(v.y, a.out + e + 1);
+        }
+        const int i0 = int(e) - int(lo);
+        if (in0) s_x[i0 + i0 / R] = v.x;
+        if (in1) s_x[i0 + 1 + (i0 + 1) / R] = v.y;
+    }
+    __syncthreads();
+
+    const int rows = min(max(n - t * R, 0), R);
+    double g[R];
+#pragma unroll
+    for (int i = 0; i < R; ++i) g[i] = i < rows ? s_x[t * (R + 1) + i] : 0.0;
+    double fl = 0.0, bl = 0.0;
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+        if (i < rows) fl = mul2_mac(r, fl, g[i]);
+        bl = mul2_mac(r, bl, g[R - 1 - i]);   // rows past `rows` are 0
+    }
+    const Mul2 pr = mul2_from_t(tpow(t1, uint32_t(rows)));   // r^rows
+
+    double fev, ftv, bev, btv;
+    Mul2 fep, bep;
+    wg_scan_pair<NT / 64, false>(fl, pr, s_v, s_h, s_l, fev, fep, ftv);
+    wg_scan_pair<NT / 64, true>(bl, pr, s_v, s_h, s_l, bev, bep, btv);
+    if (PHASE == 1) {
+        if (t == 0) {
+            coef[size_t(kb) * 2] = ftv;
+            coef[size_t(kb) * 2 + 1] = btv;
+        }
+        return;
+    }
+    const double bin = mul2_mac(bep, lr[size_t(kb) * 2 + 1], bev);
+    double fv = mul2_mac(fep, lr[size_t(kb) * 2], fev);
+    {
+        double bv = bin;
+#pragma unroll
+        for (int i = R - 1; i >= 0; --i)
+            if (i < rows) {
+                bv = mul2_mac(r, bv, g[i]);
+                g[i] = bv;
+            }
+    }
+#pragma unroll
+    for (int i = 0; i < R; ++i)
+        if (i < rows) {
+            const double gn = i + 1 < rows ? g[i + 1] : bin;
+            s_x[t * (R + 1) + i] = sd * mul2_mac(r, fv, g[i]);
+            fv = mul2_mac(r, fv - gn, g[i]);
+        }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        const uint32_t e = e0 + uint32_t(2 * NT * j);
+        if (e >= hi) continue;
+        const bool in0 = e >= lo, in1 = e + 1u < hi;
+        const int i0 = int(e) - int(lo);
+        double2 v;
+        v.x = in0 ? s_x[i0 + i0 / R] : 0.0;
+        v.y = in1 ? s_x[i0 + 1 + (i0 + 1) / R] : 0.0;
+        if (in0 && in1) stnt2(a.out + e, v);
+        else if (in0) __builtin_nontemporal_store(v.x, a.out + e);
+        else __builtin_nontemporal_store(v.y, a.out + e + 1);
+    }
+}
+
+// The interface of one line's nblk blocks in one workgroup of NW waves (line blockIdx.x): thread t walks a run of
+// consecutive blocks serially, the runs' pairs combine by the workgroup scan (multipliers r^rows of the runs), the
+// mirror closes on the line's totals, and every thread walks its run again from its carries. co, lr: [block][2][line].
+// p = 1: the one line on 16 waves (a 2^27-point line has 32768 blocks: runs of 32); p >= 2 with too few lines to
+// fill the chip a thread each (k_trib_iface): one wave a line.
+template <int NW>
+__global__ __launch_bounds__((NW * 64)) void k_blk_iface(const SpecArgs a, const double* __restrict__ co,
+                                                         double* __restrict__ lr, uint32_t nblk) {
+    constexpr int NTI = NW * 64;
+    double sigma = a.sigma;
+    if (a.skip && *a.skip) return;
+    if (a.ctl) {
+        if (a.ctl->done) return;
+        sigma = a.ctl->sigma;
+    }
+    __shared__ double s_v[NW], s_h[NW], s_l[NW];
+    const uint32_t m = a.m[a.d], t = threadIdx.x, l = blockIdx.x;
+    const size_t C = a.nlines;
+    double lamv[kMaxDims] = {0, 0, 0, 0};
+    uint32_t rest = a.q_off + l;
+    for (int jj = 0; jj < a.p - 1; ++jj) {
+        const uint32_t qd = (jj < a.p - 2) ? a.fd[jj].div(rest) : 0u;
+        lamv[jj] = a.lam[a.lam_off[jj] + (rest - qd * a.m[jj])];
+        rest = qd;
+    }
+    double c0 = a.w0, c1 = 0.0;
+    for (int Sm = 1; Sm < (1 << a.p); ++Sm) {
+        if (a.cS[Sm] == 0.0) continue;
+        double prod = sigma * a.cS[Sm];
+        for (int jj = 0; jj < a.p - 1; ++jj)
+            if ((Sm >> jj) & 1) prod *= lamv[jj];
+        if ((Sm >> (a.p - 1)) & 1) c1 += prod;
+        else c0 += prod;
+    }
+    const double D = sqrt(c0 * (c0 + 4.0 * c1));
+    const double t1 = (c0 + D) / (c0 + 2.0 * c1 + D);   // 1 - r
+    const uint32_t nlo = m / nblk;
+    const double tlo = tpow(t1, nlo);
+    const Mul2 mlo = mul2_from_t(tlo), mhi = mul2_from_t(fma(-tlo, t1, tlo + t1));
+    auto rblk = [&](uint32_t k) {
+        const uint32_t nk = uint32_t(uint64_t(m) * (k + 1) / nblk - uint64_t(m) * k / nblk);
+        return nk == nlo ? mlo : mhi;
+    };
+    const uint32_t per = (nblk + uint32_t(NTI) - 1) / uint32_t(NTI);
+    const uint32_t k0 = min(t * per, nblk), k1 = min(k0 + per, nblk);
+    double acc = 0.0, bcc = 0.0;
+    Mul2 pp{1.0, 0.0};
+    for (uint32_t k = k0; k < k1; ++k) {
+        const Mul2 rk = rblk(k);
+        acc = mul2_mac(rk, acc, co[(size_t(k) * 2) * C + l]);
+        pp = mul2_mul(pp, rk);
+    }
+    for (uint32_t k = k1; k > k0; --k) bcc = mul2_mac(rblk(k - 1), bcc, co[(size_t(k - 1) * 2 + 1) * C + l]);
+    double fev, ftv, bev, btv;
+    Mul2 fep, bep;
+    wg_scan_pair<NTI / 64, false>(acc, pp, s_v, s_h, s_l, fev, fep, ftv);
+    wg_scan_pair<NTI / 64, true>(bcc, pp, s_v, s_h, s_l, bev, bep, btv);
+    // F_{-1} = B_0 and B_m = F_{m-1}: ftv, btv are F_{m-1} and B_0 from zero carries
+    const double tm = tpow(t1, m), pm = 1.0 - tm, idet = 1.0 / (tm * (2.0 - tm));   // r^m, 1 / (1 - r^2m)
+    const double fm1 = (btv + pm * ftv) * idet, bm = (ftv + pm * btv) * idet;
+    double f = mul2_mac(fep, fm1, fev), b = mul2_mac(bep, bm, bev);
+    for (uint32_t k = k0; k < k1; ++k) {
+        lr[(size_t(k) * 2) * C + l] = f;
+        f = mul2_mac(rblk(k), f, co[(size_t(k) * 2) * C + l]);
+    }
+    for (uint32_t k = k1; k > k0; --k) {
+        lr[(size_t(k - 1) * 2 + 1) * C + l] = b;
+        b = mul2_mac(rblk(k - 1), b, co[(size_t(k - 1) * 2 + 1) * C + l]);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // k_sweep: the dim-1 transforms of a 3-D solve fused into the dim-2 line solve as two marching sweeps (round 7).
 // The factorised line solve is two first-order recursions with one constant r per (k0, k1) line, so a workgroup that
 // owns a k_dct8 strided tile (16 adjacent k0 x all m1 = 2^L points of dim 1) and marches the planes of dim 2 keeps its
@@ -4446,6 +4919,92 @@ hipError_t launch_line_sweep(const SpecPlan& sp, const Geom& g, hipStream_t s, i
     return hipGetLastError();
 }
 
+// The blocked last-dimension solve's shape (k_trib, k_tri1). p = 1: blocks of <= 4096 rows (256 threads x 16 rows).
+// p >= 2, workgroups of <= 512 threads (phase 3 holds a segment's 32 rows and the carries in registers: 1024 threads
+// leave 128 VGPRs and spill): 64-line tiles (512-B rows per wave load; <= 8 segments: blocks of <= 256 rows) where such
+// a grid has >= 256 workgroups, else 16-line tiles (<= 32 segments: <= 1024 rows), 4-line tiles for the < 16 lines of a
+// narrow 2-D mesh (<= 64 segments: <= 2048 rows); a grid short of 512 workgroups takes more blocks, down to 128 rows
+// each. blocks >= 2 forces the count.
+bool line_blocks_plan(const Geom& g, int blocks, LineBlocks* lb) {
+    const uint32_t m = g.m[g.p - 1], nlines = g.N / m;
+    *lb = LineBlocks{};
+    if (blocks < 0 || blocks == 1 || uint32_t(blocks) > m) return false;
+    auto cdiv = [](uint32_t x, uint32_t y) { return (x + y - 1) / y; };
+    if (g.p == 1) {
+        const uint32_t nb = blocks ? uint32_t(blocks) : cdiv(m, uint32_t(tri1::BL));
+        if (cdiv(m, nb) > uint32_t(tri1::BL)) return false;
+        lb->nblk = int(std::max(nb, 1u));
+        return true;
+    }
+    const uint32_t sm = uint32_t(trib::SMAX);
+    const uint32_t narrow = nlines >= 16u ? 16u : 4u, nmax = (nlines >= 16u ? 32u : 64u) * sm;   // the fallback tile
+    uint32_t tq, nb;
+    if (blocks) {
+        nb = uint32_t(blocks);
+        const uint32_t nhi = cdiv(m, nb);
+        tq = (nlines >= 64u && nhi <= 8u * sm && uint64_t(nlines / 64u) * nb >= 256u) ? 64u : narrow;
+        if (tq != 64u && nhi > nmax) return false;
+    } else {
+        nb = cdiv(m, 8u * sm);
+        if (nlines >= 64u && uint64_t(nlines / 64u) * nb >= 256u) {
+            tq = 64u;
+        } else {
+            tq = narrow;
+            nb = std::max(cdiv(m, nmax), std::min(cdiv(m, 128u), cdiv(512u, cdiv(nlines, tq))));
+        }
+    }
+    const uint32_t nhi = cdiv(m, nb);
+    lb->nblk = int(nb);
+    lb->tq = int(tq);
+    lb->sl = int(std::min(sm, nhi));
+    lb->nseg = int(cdiv(nhi, uint32_t(lb->sl)));
+    return true;
+}
+
+// one launch per phase on s: phase 1 (pairs from zero carries), the interface, phase 3 (the solve into a.out). A timed
+// pass (g_timed) spans the three launches: the start event on the first, the stop event on the last.
+static hipError_t launch_line_blocks(const SpecPlan& sp, const SpecArgs& a, hipStream_t s, bool formb) {
+    const LineBlocks& lb = sp.lb;
+    const uint32_t nblk = uint32_t(lb.nblk);
+    if (!sp.lb_coef || !sp.lb_lr || nblk < 1 || nblk > a.m[a.d]) return hipErrorInvalidValue;
+    const TimedLaunch tl = g_timed;
+    g_timed = TimedLaunch{};
+    auto go = [&](auto kern, dim3 grid, dim3 block, int phase, auto... args) {
+        if (g_launch_log.on) launch_log_push(reinterpret_cast<const void*>(kern), grid, block);
+        hipEvent_t e0 = phase == 1 ? tl.start : nullptr, e1 = phase == 3 ? tl.stop : nullptr;
+        if (e0 || e1) hipExtLaunchKernelGGL(kern, grid, block, 0, s, e0, e1, 0u, args...);
+        else hipLaunchKernelGGL(kern, grid, block, 0, s, args...);
+    };
+    if (a.p == 1) {
+        // 16-B accesses: every array on a 16-B boundary
+        uintptr_t al = reinterpret_cast<uintptr_t>(a.in) | reinterpret_cast<uintptr_t>(a.out);
+        if (formb) al |= reinterpret_cast<uintptr_t>(a.ga) | reinterpret_cast<uintptr_t>(a.gb);
+        if (al & 15u) return hipErrorInvalidValue;
+        const dim3 grid(nblk), block(tri1::NT);
+        if (formb) go(k_tri1<1, true>, grid, block, 1, a, nblk, sp.lb_coef, sp.lb_lr);
+        else go(k_tri1<1, false>, grid, block, 1, a, nblk, sp.lb_coef, sp.lb_lr);
+        go(k_blk_iface<16>, dim3(1), dim3(1024), 2, a, sp.lb_coef, sp.lb_lr, nblk);
+        if (formb) go(k_tri1<3, true>, grid, block, 3, a, nblk, sp.lb_coef, sp.lb_lr);
+        else go(k_tri1<3, false>, grid, block, 3, a, nblk, sp.lb_coef, sp.lb_lr);
+        return hipGetLastError();
+    }
+    if (formb || a.d != a.p - 1) return hipErrorInvalidValue;
+    const uint32_t tq = uint32_t(lb.tq), ntile = (a.nlines + tq - 1) / tq;
+    if (uint64_t(ntile) * nblk > 0x7fffffffull) return hipErrorInvalidValue;
+    const dim3 grid(ntile * nblk), block(tq * uint32_t(lb.nseg));
+    constexpr int SM = trib::SMAX;
+    if (tq == 64) go(k_trib<1, SM, 64, 8>, grid, block, 1, a, lb.sl, nblk, ntile, sp.lb_coef, sp.lb_lr);
+    else if (tq == 16) go(k_trib<1, SM, 16, 32>, grid, block, 1, a, lb.sl, nblk, ntile, sp.lb_coef, sp.lb_lr);
+    else go(k_trib<1, SM, 4, 64>, grid, block, 1, a, lb.sl, nblk, ntile, sp.lb_coef, sp.lb_lr);
+    // a thread a line where the lines fill the chip, else a wave a line
+    if (a.nlines >= 8192u) go(k_trib_iface, dim3((a.nlines + 255u) / 256u), dim3(256), 2, a, sp.lb_coef, sp.lb_lr, nblk);
+    else go(k_blk_iface<1>, dim3(a.nlines), dim3(64), 2, a, sp.lb_coef, sp.lb_lr, nblk);
+    if (tq == 64) go(k_trib<3, SM, 64, 8>, grid, block, 3, a, lb.sl, nblk, ntile, sp.lb_coef, sp.lb_lr);
+    else if (tq == 16) go(k_trib<3, SM, 16, 32>, grid, block, 3, a, lb.sl, nblk, ntile, sp.lb_coef, sp.lb_lr);
+    else go(k_trib<3, SM, 4, 64>, grid, block, 3, a, lb.sl, nblk, ntile, sp.lb_coef, sp.lb_lr);
+    return hipGetLastError();
+}
+
 bool dct_pcg_fusable(const Geom& g, size_t partial_words) {
     const uint32_t m = g.m[0];
     if (g.p < 2 || m < 64 || m > 4096 || (m & (m - 1)) != 0 || probe_env("MVTV_DCT_LDS") || probe_env("MVTV_PCGS_NINE"))
@@ -4500,6 +5059,9 @@ hipError_t launch_dct_pass(const SpecPlan& sp, const Geom& g, hipStream_t s, int
         return !(e && std::atoi(e) == 0);
     }();
     a.pair16 = pair16 ? 1 : 0;
+    // the line solve along the last dimension in blocks: any length (mvtv_problem_line_blocks forces it at any m)
+    if (sp.lb.nblk > 0 && mode == SPEC_MID && d == g.p - 1 && !fold && !(pf && pf->mode))
+        return launch_line_blocks(sp, a, s, formb);
     if (m > 4096) return hipErrorInvalidValue;
     if (a.fold && (!formb || !gb || !ctl || (1u << a.L) != m || (1u << a.ls) != a.stride || a.L < 3 ||
                    probe_env("MVTV_DCT_LDS") || mode == SPEC_MID))
