@@ -12,6 +12,7 @@ import pytest
 
 from conftest import load_golden, log_parity
 from oracle import mvtv_oracle as O
+from pcg_ref import pcg_iterates
 
 mv = pytest.importorskip("multivartv_amd")
 pytestmark = pytest.mark.gpu
@@ -96,20 +97,7 @@ def _jacobi_pcg(D, w, sigma, b, x, k):
     """k iterations of textbook Jacobi-PCG (numpy): the iterates the fused 3-D kernel's single-reduction form
     reproduces up to rounding (rcpp-code/MultivarTV/src/solvers.cpp:113 solves the same system directly)."""
     dinv = 1.0 / (w + sigma * np.asarray((D.T @ D).diagonal()).ravel())
-    x = x.copy()
-    r = b - O.apply_A(D, w, sigma, x)
-    z = dinv * r
-    p = z.copy()
-    rz = r @ z
-    for _ in range(k):
-        q = O.apply_A(D, w, sigma, p)
-        al = rz / (p @ q)
-        x += al * p
-        r -= al * q
-        z = dinv * r
-        rz, rz0 = r @ z, rz
-        p = z + (rz / rz0) * p
-    return x
+    return pcg_iterates(lambda v: O.apply_A(D, w, sigma, v), lambda r: dinv * r, b, x, k)[0][-1]
 
 
 @pytest.mark.parametrize("weighted", [False, True])
