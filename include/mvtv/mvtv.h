@@ -185,7 +185,15 @@ mvtv_status mvtv_fitted(mvtv_problem* prob, const int64_t* mesh_index, int64_t n
  * axes: the mesh's sorted axis values, m[0] values of dim 0, then m[1] of dim 1, ... (the linspace
  * axes of create_mesh, rcpp…/utils.cpp:234-254; mesh rows in column-major order). data: n x p,
  * column-major (arma::mat). mesh_index_out [n] (may be NULL): the column-major mesh node of each
- * point, i.e. the column of the 1 in row i of O. */
+ * point, i.e. the column of the 1 in row i of O.
+ * Every coordinate must be finite (NaN or +-inf: MVTV_BAD_ARG; the reference maps an infinite point to node 0).
+ * The indices equal the reference's brute-force scan for every point with, on every axis j,
+ *     g_j (2 r_j + g_j) >= 4 (p + 2) 2^-53 sum_i R_i^2
+ * g_j: smallest spacing of axis j; r_j: distance from x_j to its nearest node of axis j; R_i: distance from x_i to
+ * the farther end of the axis-i cell that holds it (to the nearest node when x_i lies outside the axis). That is
+ * every point inside the mesh box when the spacings lie within 2^25 / sqrt(p (p + 2)) of one another, and points
+ * outside it up to about 2^25.5 / sqrt(p + 2) smallest spacings away; farther out float64 absorbs the other axes'
+ * squared distances, whole rows of nodes tie, and the scan's first minimum need not be a corner of the point's cell. */
 /* nearest1 / nearest_interp_matrix (rcpp…/utils.cpp:267-304): first nearest mesh row per point */
 mvtv_status mvtv_nearest(mvtv_problem* prob, const double* axes, const double* data, int64_t n,
                          int64_t* mesh_index_out);

@@ -1764,7 +1764,7 @@ struct TmpDev {
     T* get() const { return static_cast<T*>(p); }
 };
 
-// axes checked on the host (finite, ascending per dim), then axes and data copied over and the
+// axes (finite, ascending per dim) and data (finite) checked on the host, then axes and data copied over and the
 // nearest node of every point computed into key (and idx when requested)
 mvtv_status nearest_on_device(mvtv_problem* P, const double* axes, const double* data, int64_t n, TmpDev& key,
                               TmpDev& idx, bool want_idx) {
@@ -1781,7 +1781,7 @@ mvtv_status nearest_on_device(mvtv_problem* P, const double* axes, const double*
         na += P->g.m[j];
     }
     for (int64_t i = 0; i < n * p; ++i)
-        if (std::isnan(data[i])) return fail(MVTV_BAD_ARG, "NaN in data");
+        if (!std::isfinite(data[i])) return fail(MVTV_BAD_ARG, "NaN or infinite value in data");
     TmpDev daxes, ddata;
     HIP_TRY(hipMalloc(&daxes.p, na * sizeof(double)));
     HIP_TRY(hipMalloc(&ddata.p, size_t(std::max<int64_t>(n * p, 1)) * sizeof(double)));

@@ -9,6 +9,21 @@
 // a binary search per axis finds the bracket, then the 2^p candidate distances are summed in the
 // reference's order (dims 0..p-1, no fused multiply-add) and the first minimum in mesh-row order wins.
 //
+// Domain of identical indices. Some corner always attains the scan's minimum value (float64 addition and
+// multiplication are monotone); its index is the scan's as long as no node outside the bracket ties with a
+// corner. A computed distance lies within (p + 2) u of the exact one (u = 2^-53), and moving an out-of-bracket
+// coordinate of axis j to the nearer bracket end lowers the exact distance by at least g_j (2 r_j + g_j), so
+// the indices are the brute-force scan's for every finite point with, on every axis j,
+//     g_j (2 r_j + g_j) >= 4 (p + 2) 2^-53 sum_i R_i^2
+// (g_j the smallest spacing of axis j, r_j the distance from x_j to its nearest node on axis j, R_i the
+// distance from x_i to the farther end of its bracket, to the nearest node when x_i is outside the axis):
+// any point inside the box when the spacings lie within 2^25 / sqrt(p (p + 2)) of one another, and outside it
+// up to about 2^25.5 / sqrt(p + 2) smallest spacings away. Farther out float64 absorbs the other axes'
+// squared distances, whole rows of nodes tie, and the scan takes the lowest index of all N nodes where this
+// kernel takes the lowest corner (axes 0..4 and 0..3, x = (3.7, 1e9): 15 against 18). Points with a NaN or an
+// infinite coordinate have no nearest node (the scan returns node 0 for every distance inf): the host refuses
+// them (nearest_on_device, MVTV_BAD_ARG).
+//
 // O^T y: y is sorted by mesh index with a stable radix sort (rocPRIM), then each run of equal keys is
 // summed left to right, so every node's sum adds the same values in the same order as the reference's
 // sparse product (and numpy's bincount): bit-identical, and deterministic from run to run, which a
