@@ -88,8 +88,9 @@ typedef enum mvtv_theta_solver {
     MVTV_SOLVER_AUTO = 0,      /* SPECTRAL where it is exact; else PCG_SPECTRAL on the same meshes; else PCG */
     MVTV_SOLVER_PCG = 1,       /* Jacobi-PCG on the 3^p-point stencil, warm-started, pcg_rtol */
     MVTV_SOLVER_SPECTRAL = 2,  /* direct: cosine transforms + a tridiagonal solve along the last dim. Exact for
-                                  W = I (mesh == data) with m_j <= 4096 for j < p - 1 (FFT plans for lengths with
-                                  prime factors 2, 3, 5, 7, Bluestein's chirp-z for any other) and a last dimension
+                                  W = I (mesh == data) with, for j < p - 1, m_j <= 4096 (FFT plans for lengths with
+                                  prime factors 2, 3, 5, 7, Bluestein's chirp-z for any other) or m_j = a * b with
+                                  both factors <= 4096 and 2-3-5-7-smooth (two passes, one GPU), and a last dimension
                                   of any length (never transformed: a line solve, in blocks past 4096 rows);
                                   MVTV_BAD_ARG otherwise */
     MVTV_SOLVER_PCG_SPECTRAL = 3 /* PCG preconditioned by S (mean(W) I + sigma D^T D) S, its middle factor inverted
@@ -132,8 +133,10 @@ int32_t mvtv_problem_blocks(const mvtv_problem* prob);
 mvtv_status mvtv_problem_block_info(const mvtv_problem* prob, int32_t k, int32_t* code, int32_t* sprime, double* weight);
 /* new O^T y and W for the same mesh (CV folds re-run create_cache_objects, rcpp…/solvers.cpp:347-348) */
 mvtv_status mvtv_problem_set_data(mvtv_problem* prob, const double* oty, const double* wdiag);
-/* 1 if MVTV_SOLVER_SPECTRAL applies to this problem (W = I, m_j <= 4096 for j < p - 1; the last dimension any length
- * on one GPU), else 0 */
+/* 1 if MVTV_SOLVER_SPECTRAL applies to this problem (W = I; every m_j, j < p - 1, <= 4096 or, on one GPU, a product of
+ * two 2-3-5-7-smooth factors <= 4096; the last dimension any length on one GPU), else 0. What stays refused: a leading
+ * dimension above 4096 with a prime factor >= 11 (4099, 4100 = 2^2 5^2 41), and any dimension above 4096 on a slab
+ * rank but the last of G >= 2. */
 int32_t mvtv_problem_spectral_ok(const mvtv_problem* prob);
 /* The line solve along the last dimension in `blocks` blocks [floor(m k / blocks), floor(m (k + 1) / blocks)) of every
  * line: per-block recursion sums, an interface step that gives every block its carries and closes the mirror, and a
@@ -144,6 +147,16 @@ int32_t mvtv_problem_spectral_ok(const mvtv_problem* prob);
  * p = 1; 1024 at p >= 2, 2048 with fewer than 16 lines), a slab rank, or a mesh the spectral solve does not accept. Waits for the problem's stream;
  * (re)allocates 4 * blocks * N / m_last doubles of scratch. */
 mvtv_status mvtv_problem_line_blocks(mvtv_problem* prob, int32_t blocks);
+/* Cosine transforms along dimension dim (< p - 1) in two passes over the factorisation m_dim = a * (m_dim / a).
+ * a = 0: automatic (the default: only where m_dim > 4096, the library's factorisation). a >= 2: that first
+ * factor at any m_dim (tests; an A/B against the one-workgroup kernels; the passes that hold a whole line of a leading
+ * dimension in one workgroup, the marching line sweeps, the fused plane pass, the folded right-hand side and the
+ * PCG-fused passes, rest meanwhile). The frequencies of a split dimension stay in the order position
+ * (m_dim / a) * k1 + k2 <-> k = k1 + a * k2 between the forward and the inverse pass. MVTV_BAD_ARG for dim < 0 or
+ * >= p - 1, a = 1, a < 0, a that does not divide m_dim, a factor above 4096 or with a prime factor >= 11, a slab
+ * rank, or a mesh the spectral solve does not accept. Waits for the problem's stream; (re)allocates the splits' tables
+ * (32 B * (4096 + m_dim / 1024) + 20 B * (a + b) a dimension) and one scratch vector of <= N + m_dim doubles. */
+mvtv_status mvtv_problem_dct_split(mvtv_problem* prob, int32_t dim, int32_t a);
 /* The marching line sweeps of the 3-D spectral solve (m_1 = 512, m_0 a multiple of 16, one GPU): the dim-1 transforms
  * fused into the dim-2 line solve, two passes over the vector and an interface step over `chunks` chunks of dim 2 in
  * place of three passes. mode -1: automatic (the default: meshes of more than 2^24 nodes that fill the GPU with

@@ -84,6 +84,7 @@ SIGNATURES = {
     "mvtv_problem_spectral_ok": (C.c_int32, [C.c_void_p]),
     "mvtv_problem_line_sweep": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "mvtv_problem_line_blocks": (C.c_int, [C.c_void_p, C.c_int32]),
+    "mvtv_problem_dct_split": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "mvtv_admm": (C.c_int, [C.c_void_p, C.POINTER(AdmmOpts), C.c_double, _dp, _dp, _dp, C.POINTER(AdmmStats)]),
     "mvtv_state_set": (C.c_int, [C.c_void_p, _dp, _dp, C.c_double]),
     "mvtv_state_get": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
@@ -380,6 +381,11 @@ class Problem:
         """The line solve along the last dimension in blocks: 0 automatic (only where m_last > 4096), >= 2 that many
         blocks at any m_last (mvtv_problem_line_blocks)."""
         _check(lib().mvtv_problem_line_blocks(self._h, int(blocks)))
+
+    def dct_split(self, dim, a=0):
+        """The cosine transforms along dimension dim < p - 1 in two passes over m_dim = a * (m_dim / a): 0 automatic
+        (only where m_dim > 4096), >= 2 that first factor at any m_dim (mvtv_problem_dct_split)."""
+        _check(lib().mvtv_problem_dct_split(self._h, int(dim), int(a)))
 
     def solve_spectral(self, sigma, b):
         bb = _f64(b, self.N)

@@ -183,9 +183,11 @@ void free_all(mvtv_problem* P) {
     if (P->st) (void)hipFree(P->st);
     if (P->ctl) (void)hipFree(P->ctl);
     if (P->host_ctl) (void)hipHostFree(P->host_ctl);
-    for (double* t : {P->spec.tw, P->spec.twq, P->spec.lam, P->spec.blu, P->spec.lb_coef, P->spec.lb_lr})
+    for (double* t : {P->spec.tw, P->spec.twq, P->spec.lam, P->spec.blu, P->spec.lb_coef, P->spec.lb_lr, P->spec.stw,
+                      P->spec.sscr})
         if (t) (void)hipFree(t);
     if (P->spec.perm) (void)hipFree(P->spec.perm);
+    if (P->spec.srev) (void)hipFree(P->spec.srev);
     P->spec = SpecPlan{};
     if (P->host_red) (void)hipHostFree(P->host_red);
     for (auto& pd : P->pending) {
@@ -438,8 +440,15 @@ mvtv_status spectral_plan(mvtv_problem* P) {
         sp.tw_off[j] = uint32_t(tw.size());
         sp.twq_off[j] = uint32_t(twq.size());
         sp.lam_off[j] = uint32_t(lam.size());
+        sp.perm_off[j] = uint32_t(perm.size());
         // a last dimension longer than 4096 is never transformed (the blocked line solve reads no table of it)
         if (P->spec_long && j == P->g.p - 1) continue;
+        // a leading dimension longer than 4096 takes the two-pass transform (dct_split_setup: its tables, and this
+        // dimension's eigenvalues in its frequency order): no length-m twiddle table
+        if (m > kSplitMax) {
+            lam.resize(lam.size() + m, 0.0);
+            continue;
+        }
         for (uint32_t k = 0; k < m; ++k) {
             const long double a = -2.0L * pi * k / m;
             tw.push_back(double(cosl(a)));
@@ -488,12 +497,12 @@ mvtv_status spectral_plan(mvtv_problem* P) {
         return MVTV_OK;
     };
     if (!blu.empty()) MVTV_TRY(up(&sp.blu, blu));
-    if (tw.empty()) {   // p = 1 with a long line: no table at all; the passes still take the pointers
+    if (tw.empty()) {   // only long dimensions (p = 1 with a long line: no table at all): the passes still take the pointers
         tw.assign(2, 0.0);
         twq.assign(2, 0.0);
-        lam.assign(1, 0.0);
         perm.assign(1, 0u);
     }
+    if (lam.empty()) lam.assign(1, 0.0);
     MVTV_TRY(up(&sp.tw, tw));
     MVTV_TRY(up(&sp.twq, twq));
     MVTV_TRY(up(&sp.lam, lam));
@@ -541,7 +550,7 @@ mvtv_status line_sweep_setup(mvtv_problem* P, int mode, int chunks) {
 // pairs and carries live in the plan, allocated here when the solve is in use.
 mvtv_status line_blocks_setup(mvtv_problem* P, int blocks) {
     if (P->slab || !P->spec_mesh)
-        return fail(MVTV_BAD_ARG, "line_blocks: not a slab rank, and m_j <= 4096 for j < p - 1");
+        return fail(MVTV_BAD_ARG, "line_blocks: not a slab rank, and every m_j, j < p - 1, <= 4096 or a product of two 2-3-5-7-smooth factors <= 4096");
     const uint32_t mlast = P->g.m[P->g.p - 1];
     if (blocks < 0 || blocks == 1 || uint32_t(blocks) > mlast)
         return fail(MVTV_BAD_ARG, "line_blocks: 0 or 2 <= blocks <= m_last");
@@ -567,7 +576,107 @@ mvtv_status line_blocks_setup(mvtv_problem* P, int blocks) {
     return MVTV_OK;
 }
 
-bool sweeps_on(const mvtv_problem* P) { return P->ls_chunks > 0 && P->spec.lb.nblk == 0; }
+// a factor of a split: 2 <= n <= 4096 with a 2-3-5-7 plan
+bool split_factor_ok(uint32_t n) {
+    int rad[8], nrad = 0;
+    return n >= 2 && n <= kSplitMax && dct_radix_plan(n, rad, &nrad);
+}
+
+// The two-pass cosine transforms of the leading dimensions (mvtv_spectral.hip k_dsc / k_dsr): dimension j takes
+// m_j = a (m_j / a) with a = split_forced[j], or the library's factorisation where m_j > 4096. (Re)builds the splits'
+// tables (evaluated in long double) and their scratch, and stores lam_j of every leading dimension in the order its
+// forward pass leaves the frequencies: position b k1 + k2 holds k = k1 + a k2 (the natural order without a split).
+mvtv_status dct_split_setup(mvtv_problem* P) {
+    SpecPlan& sp = P->spec;
+    const int p = P->g.p;
+    const long double pi = 3.141592653589793238462643383279502884L;
+    HIP_TRY(hipStreamSynchronize(P->stream));   // no launch may still read the tables or the scratch
+    if (sp.stw) (void)hipFree(sp.stw);
+    if (sp.srev) (void)hipFree(sp.srev);
+    sp.stw = nullptr;
+    sp.srev = nullptr;
+    std::vector<double> tw;
+    std::vector<uint32_t> rev;
+    size_t scratch = 0;
+    auto fft_tables = [&](uint32_t n, uint32_t* tw_off, uint32_t* rev_off) {
+        *tw_off = uint32_t(tw.size());
+        *rev_off = uint32_t(rev.size());
+        int rad[8], nrad = 0;
+        (void)dct_radix_plan(n, rad, &nrad);
+        for (uint32_t k = 0; k < n; ++k) {
+            const long double ang = -2.0L * pi * k / n;
+            tw.push_back(double(cosl(ang)));
+            tw.push_back(double(sinl(ang)));
+            uint32_t r = k, pos = 0;   // digit-reversed place of sample k (spectral_plan's rule)
+            for (int st = nrad - 1; st >= 0; --st) {
+                uint32_t mul = 1;
+                for (int u = 0; u < st; ++u) mul *= uint32_t(rad[u]);
+                pos += (r % uint32_t(rad[st])) * mul;
+                r /= uint32_t(rad[st]);
+            }
+            rev.push_back(pos);
+        }
+    };
+    auto hilo = [&](uint64_t J, uint64_t M4) {   // e^{-2 pi i J / M4} as (re, im) hi then lo
+        const long double ang = -2.0L * pi * (long double)(J % M4) / (long double)M4;
+        const long double c = cosl(ang), sn = sinl(ang);
+        const double ch = double(c), sh = double(sn);
+        tw.push_back(ch);
+        tw.push_back(sh);
+        tw.push_back(double(c - (long double)ch));
+        tw.push_back(double(sn - (long double)sh));
+    };
+    for (int j = 0; j < p - 1; ++j) {
+        const uint32_t m = P->g.m[j];
+        DctSplit& ds = sp.split[j];
+        ds = DctSplit{};
+        const uint32_t a = P->split_forced[j] ? uint32_t(P->split_forced[j]) : (m > kSplitMax ? dct_split_auto(m) : 0u);
+        if (m > kSplitMax && a == 0) return fail(MVTV_BAD_ARG, "dct_split: no factorisation");
+        std::vector<double> lam(m);
+        for (uint32_t pos = 0; pos < m; ++pos) {
+            const uint32_t k = a ? pos / (m / a) + a * (pos % (m / a)) : pos;
+            const long double sn = sinl(pi * k / (2.0L * m));
+            lam[pos] = double(4.0L * sn * sn);
+        }
+        HIP_TRY(hipMemcpy(sp.lam + sp.lam_off[j], lam.data(), size_t(m) * sizeof(double), hipMemcpyHostToDevice));
+        if (a == 0) continue;
+        ds.a = a;
+        ds.b = m / a;
+        fft_tables(ds.a, &ds.twa, &ds.reva);
+        fft_tables(ds.b, &ds.twb, &ds.revb);
+        const uint64_t M4 = 4 * uint64_t(m);
+        ds.t1 = uint32_t(tw.size());
+        for (uint64_t i = 0; i * 4096 < M4; ++i) hilo(i * 4096, M4);
+        ds.t2 = uint32_t(tw.size());
+        for (uint64_t i = 0; i < 4096; ++i) hilo(i, M4);
+        const size_t nlines = P->g.N / m;
+        scratch = std::max(scratch, 2 * ((nlines + 1) / 2) * size_t(m));
+    }
+    if (scratch > sp.sscr_cap || scratch == 0) {
+        if (sp.sscr) (void)hipFree(sp.sscr);
+        sp.sscr = nullptr;
+        sp.sscr_cap = 0;
+        if (scratch) {
+            MVTV_TRY(alloc(&sp.sscr, scratch));
+            sp.sscr_cap = scratch;
+        }
+    }
+    if (tw.empty()) return MVTV_OK;
+    MVTV_TRY(alloc(&sp.stw, tw.size()));
+    HIP_TRY(hipMemcpy(sp.stw, tw.data(), tw.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&sp.srev), rev.size() * sizeof(uint32_t)));
+    HIP_TRY(hipMemcpy(sp.srev, rev.data(), rev.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return MVTV_OK;
+}
+
+// a leading dimension runs in two passes: the passes that hold a whole line of it in one workgroup rest
+bool split_on(const mvtv_problem* P) {
+    for (int j = 0; j < P->g.p - 1; ++j)
+        if (P->spec.split[j].a > 0) return true;
+    return false;
+}
+
+bool sweeps_on(const mvtv_problem* P) { return P->ls_chunks > 0 && P->spec.lb.nblk == 0 && !split_on(P); }
 
 // down sweep, interface, up sweep, in place on x (the dim-0 coefficients of the right-hand side, then of the solve)
 mvtv_status line_sweeps(mvtv_problem* P, double* x, double sigma, double w0, const AdmmCtl* ctl, const int32_t* skip) {
@@ -597,7 +706,7 @@ mvtv_status spectral_solve(mvtv_problem* P, double sigma, const double* oty, con
     const int mid = (mid_env >= 1 && mid_env < p) ? mid_env : p - 1;
     // 3-D: dim 2 forward (b formed on load), the two marching passes (dim-0 transforms + the dim-1 line solves),
     // dim 2 inverse: 9N words instead of 11N
-    if (!P->slab && march_ok(P->g)) {
+    if (!P->slab && march_ok(P->g) && !split_on(P)) {
         int h = P->tstart(ga ? (fold ? MVTV_K_DCT_FOLD : MVTV_K_DCT_FIRST) : MVTV_K_DCT);
         if (ga && fold)
             HIP_TRY(launch_dct_pass(P->spec, P->g, P->stream, 0, 2, oty, ga, 1.0, gb, 0.0, x, sigma, w0, ctl, 0, 0.0, skip,
@@ -651,7 +760,7 @@ mvtv_status spectral_solve(mvtv_problem* P, double sigma, const double* oty, con
     if (rev) std::reverse(order, order + n);
     order[n++] = mid;
     // m0 = m1 <= 128: dims 0 and 1 in one pass each way (k_plane8: the plane stays on chip between them)
-    const bool plane = !rev && mid >= 2 && plane_pass_ok(P->g);
+    const bool plane = !rev && mid >= 2 && plane_pass_ok(P->g) && !split_on(P);
     if (plane) {
         const int h = P->tstart(ga ? (fold ? MVTV_K_DCT_FOLD : MVTV_K_DCT_FIRST) : MVTV_K_DCT);
         if (ga && fold)
@@ -738,7 +847,7 @@ mvtv_status pcgs_solve(mvtv_problem* P, double sigma, const double* oty, const d
     // power-of-two m_0 >= 64: the x / r update rides on the preconditioner's first (d = 0) pass and the
     // s^-1 scaling with r.z, |r|^2 on its last, seven launches per iteration instead of nine
     const size_t pwords = size_t(std::max(kMaxGrid, kMaxCgBlocks)) * kMaxRed;
-    const bool fused7 = dct_pcg_fusable(P->g, pwords);
+    const bool fused7 = dct_pcg_fusable(P->g, pwords) && !split_on(P);
     auto enqueue7 = [&]() -> mvtv_status {
         const int pdim = P->g.p;
         int np_last = 0;
@@ -1002,17 +1111,19 @@ mvtv_status problem_create_impl(const mvtv_problem_desc* d, const mvtv_slab_desc
         return s;
     }
     P->host_st = reinterpret_cast<PcgState*>(P->host_red + 16);
-    // cosine transforms of any length <= 4096: FFT plans for 2-3-5-7 lengths, Bluestein (k_dctb) for the rest. The last
-    // dimension is never transformed: on one GPU it may have any length (spec_long: the blocked line solve); a slab
-    // rank keeps the old rule (its loop has the substructured solve over the ranks)
+    // cosine transforms of any length <= 4096: FFT plans for 2-3-5-7 lengths, Bluestein (k_dctb) for the rest; a longer
+    // leading dimension with a factorisation a * b, both 2-3-5-7-smooth and <= 4096, in two passes (dct_split_setup).
+    // The last dimension is never transformed: on one GPU it may have any length (spec_long: the blocked line solve); a
+    // slab rank keeps the old rule for every dimension (its loop has the substructured solve over the ranks)
     P->spec_mesh = P->spec_pow2 = P->spec_lead = true;
     P->spec_long = false;
     for (int j = 0; j < p; ++j) {
         const uint32_t mj = uint32_t(mg[j]);
         if (mj > 4096) {
-            if (j < p - 1) P->spec_lead = false;
+            const bool split = j < p - 1 && !P->slab && dct_split_auto(mj) != 0;
+            if (j < p - 1 && !split) P->spec_lead = false;
             if (j == p - 1 && !P->slab) P->spec_long = true;
-            else P->spec_mesh = false;
+            else if (!split) P->spec_mesh = false;
         }
         if ((mj & (mj - 1)) != 0) P->spec_pow2 = false;
     }
@@ -1026,6 +1137,7 @@ mvtv_status problem_create_impl(const mvtv_problem_desc* d, const mvtv_slab_desc
         s = line_sweep_setup(P, (e && std::atoi(e) == 0) ? 0 : -1, 0);
     }
     if (s == MVTV_OK && P->spec_long) s = line_blocks_setup(P, 0);
+    if (s == MVTV_OK && P->spec_mesh && !P->slab) s = dct_split_setup(P);
     P->e3d = edge3d_ok(g);
     if (s == MVTV_OK && P->e3d && g.p == 4 && gather4_ok(g)) s = alloc(&P->g4, 4 * size_t(N));
     P->f3d = fused3d_ok(g);   // slab problems too: the fused pass runs on the owned planes (Geom.ibeg/iend)
@@ -1086,6 +1198,20 @@ mvtv_status mvtv_problem_line_blocks(mvtv_problem* P, int32_t blocks) {
     if (!P) return fail(MVTV_BAD_ARG, "null problem");
     DeviceGuard dg(P->device);
     return line_blocks_setup(P, blocks);
+}
+
+mvtv_status mvtv_problem_dct_split(mvtv_problem* P, int32_t dim, int32_t a) {
+    if (!P) return fail(MVTV_BAD_ARG, "null problem");
+    DeviceGuard dg(P->device);
+    if (P->slab || !P->spec_mesh)
+        return fail(MVTV_BAD_ARG, "dct_split: not a slab rank, and a mesh the spectral solve accepts");
+    if (dim < 0 || dim >= P->g.p - 1) return fail(MVTV_BAD_ARG, "dct_split: 0 <= dim < p - 1");
+    const uint32_t m = P->g.m[dim];
+    if (a != 0 && (a < 2 || uint32_t(a) >= m || m % uint32_t(a) != 0 || !split_factor_ok(uint32_t(a)) ||
+                   !split_factor_ok(m / uint32_t(a))))
+        return fail(MVTV_BAD_ARG, "dct_split: a = 0, or m_dim = a * b with both factors 2-3-5-7-smooth in [2, 4096]");
+    P->split_forced[dim] = a;
+    return dct_split_setup(P);
 }
 
 mvtv_status mvtv_problem_block_info(const mvtv_problem* P, int32_t k, int32_t* code, int32_t* sprime, double* weight) {
@@ -1188,9 +1314,9 @@ mvtv_status mvtv_admm_run(mvtv_problem* P, const mvtv_admm_opts* opts_in, double
     if (o.theta_solver < MVTV_SOLVER_AUTO || o.theta_solver > MVTV_SOLVER_PCG_SPECTRAL)
         return fail(MVTV_BAD_ARG, "theta_solver");
     if (o.theta_solver == MVTV_SOLVER_SPECTRAL && !spectral_ok(P))
-        return fail(MVTV_BAD_ARG, "spectral theta-solve needs W = I and m_j <= 4096 for j < p - 1");
+        return fail(MVTV_BAD_ARG, "spectral theta-solve needs W = I and every m_j, j < p - 1, <= 4096 or a product of two 2-3-5-7-smooth factors <= 4096");
     if (o.theta_solver == MVTV_SOLVER_PCG_SPECTRAL && (!P->spec_mesh || P->wmode == W_NONE))
-        return fail(MVTV_BAD_ARG, "spectral preconditioner needs m_j <= 4096 for j < p - 1");
+        return fail(MVTV_BAD_ARG, "spectral preconditioner needs every m_j, j < p - 1, <= 4096 or a product of two 2-3-5-7-smooth factors <= 4096");
     const bool spectral = o.theta_solver == MVTV_SOLVER_SPECTRAL ||
                           (o.theta_solver == MVTV_SOLVER_AUTO && spectral_ok(P));
     // AUTO with W != I on a spectral mesh: PCG with the spectral preconditioner (K an order of magnitude
@@ -1331,13 +1457,14 @@ mvtv_status mvtv_admm_run(mvtv_problem* P, const mvtv_admm_opts* opts_in, double
         // the next solve's first pass reads oty and s (2N words) instead of oty, D^T alpha and D^T u (3N); after a
         // control step that changed rho it forms oty + (rho'/rho) s + rho' (c - 1) D^T u (AdmmCtl::fold_ka / _kb)
         // (the first pass transforms dim 0, or dim 2 on k_march meshes)
-        const uint32_t m0 = (!P->slab && march_ok(P->g)) ? P->g.m[2] : P->g.m[0];
+        const bool marching = !P->slab && march_ok(P->g) && !split_on(P);
+        const uint32_t m0 = marching ? P->g.m[2] : P->g.m[0];
         const bool fold_path = fused ? (P->g.p == 2 || P->g.p == 3)
                                      : (P->g.p == 4 && P->e3d && P->g4 != nullptr && gather4_ok(P->g));   // two-pass 4-D
         // on k_march meshes the folded first pass runs along dim 2 at stride m0 * m1, which must be a power of two too
-        const uint64_t fold_stride = (!P->slab && march_ok(P->g)) ? uint64_t(P->g.m[0]) * P->g.m[1] : 1;
+        const uint64_t fold_stride = marching ? uint64_t(P->g.m[0]) * P->g.m[1] : 1;
         const bool fold = fold_path && variant == MVTV_VARIANT_RCPP && m0 >= 8 && m0 <= 4096 &&
-                          (m0 & (m0 - 1)) == 0 && (fold_stride & (fold_stride - 1)) == 0 &&
+                          (m0 & (m0 - 1)) == 0 && (fold_stride & (fold_stride - 1)) == 0 && !split_on(P) &&
                           !probe_env("MVTV_FOLD_OFF") && !probe_env("MVTV_DCT_LDS") && !probe_env("MVTV_DCT_MID");
         auto enqueue = [&](int j) -> mvtv_status {
             double* gp = gbuf[j & 1];
@@ -2057,7 +2184,7 @@ mvtv_status mvtv_lambda_max_cpp(mvtv_problem* P, double* out, int32_t* iters) {
 
 mvtv_status mvtv_solve_spectral(mvtv_problem* P, double sigma, const double* b, double* x_out) {
     if (!P || !b || !x_out) return fail(MVTV_BAD_ARG, "null argument");
-    if (!spectral_ok(P)) return fail(MVTV_BAD_ARG, "spectral theta-solve needs W = I and m_j <= 4096 for j < p - 1");
+    if (!spectral_ok(P)) return fail(MVTV_BAD_ARG, "spectral theta-solve needs W = I and every m_j, j < p - 1, <= 4096 or a product of two 2-3-5-7-smooth factors <= 4096");
     DeviceGuard dg(P->device);
     double* dx = nullptr;
     MVTV_TRY(alloc(&dx, P->g.N));

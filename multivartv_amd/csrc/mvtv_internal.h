@@ -308,8 +308,25 @@ hipError_t launch_apply_D_padded(const Geom& g, int order, const Launch& L, cons
 struct LineBlocks {
     int nblk = 0, tq = 0, sl = 0, nseg = 0;
 };
+// The two-pass ("four-step") cosine transform of a leading dimension over m = a * b (k_dsc, k_dsr), a = 0: the
+// resident transform. Offsets into SpecPlan::stw (doubles) and SpecPlan::srev.
+struct DctSplit {
+    uint32_t a = 0, b = 0;
+    uint32_t twa = 0, twb = 0;     // a / b complex FFT twiddles e^{-2 pi i k/a}, e^{-2 pi i k/b}
+    uint32_t t1 = 0, t2 = 0;       // e^{-2 pi i J/4m} as hi + lo pairs (re, im, re_lo, im_lo): T1[J >> 12] * T2[J & 4095]
+    uint32_t reva = 0, revb = 0;   // digit-reversed positions of the length-a / length-b plans
+};
+constexpr uint32_t kSplitMax = 4096;   // the longest factor (and the longest resident line)
+// the library's factorisation of a 2-3-5-7-smooth m: the largest a <= sqrt(m) with m / a <= kSplitMax; 0: none
+uint32_t dct_split_auto(uint32_t m);
 // Spectral theta-solve tables (mvtv_spectral.hip), device-resident, offsets in doubles.
 struct SpecPlan {
+    DctSplit split[kMaxDims];
+    double* stw = nullptr;       // the splits' twiddle tables
+    uint32_t* srev = nullptr;
+    double* sscr = nullptr;      // the splits' scratch between their two passes: sscr_cap doubles (<= N + m_j)
+    size_t sscr_cap = 0;
+    uint32_t perm_off[kMaxDims] = {0, 0, 0, 0};   // per dim into perm
     // the blocked last-dimension solve (lb.nblk > 0: SPEC_MID along d = p - 1 takes it): the blocks' pairs and
     // carries, [block][2][line] each, lb_cap doubles
     LineBlocks lb;
@@ -318,7 +335,7 @@ struct SpecPlan {
     double* tw = nullptr;     // per dim: m_j complex FFT twiddles e^{-2 pi i k/m_j}
     double* twq = nullptr;    // per dim: m_j complex twiddles e^{-i pi k/(2 m_j)}
     double* lam = nullptr;    // per dim: m_j eigenvalues 4 sin^2(pi k/(2 m_j)) of the Neumann Laplacian
-    uint32_t* perm = nullptr; // per dim (at lam_off): position of sample k in the mixed-radix FFT's input order
+    uint32_t* perm = nullptr; // per dim (at perm_off): position of sample k in the mixed-radix FFT's input order
     uint32_t tw_off[kMaxDims] = {0, 0, 0, 0}, twq_off[kMaxDims] = {0, 0, 0, 0}, lam_off[kMaxDims] = {0, 0, 0, 0};
     // lengths without a 2-3-5-7 plan (Bluestein, k_dctb): per such dim, at blu_off (doubles), m complex chirp values
     // e^{-i pi n^2/m}, then M values each of the forward and inverse kernels' transforms / M, then M twiddles
@@ -375,7 +392,9 @@ bool dct_pcg_fusable(const Geom& g, size_t partial_words);
 bool dct_radix_plan(uint32_t m, int* rad, int* nrad);
 // mode 0 forward DCT-II, 1 inverse (DCT-III, unnormalised), 2 forward + divide by mu * N + inverse;
 // ga != nullptr forms the input as in + ca*ga + cb*gb. In place (in == out) is allowed. m_d <= 4096, except mode 2
-// along d = p - 1 while sp.lb.nblk > 0: the blocked line solve (three launches; p = 1: 16-B aligned arrays).
+// along d = p - 1 while sp.lb.nblk > 0: the blocked line solve (three launches; p = 1: 16-B aligned arrays), and modes
+// 0 / 1 along a dimension with sp.split[d].a > 0: the two-pass transform (two launches through sp.sscr; its
+// frequencies stay in the order position b k1 + k2 <-> k = k1 + a k2, the order of that dimension's lam table).
 hipError_t launch_dct_pass(const SpecPlan& sp, const Geom& g, hipStream_t s, int mode, int d, const double* in,
                            const double* ga, double ca, const double* gb, double cb, double* out, double sigma,
                            double w0, const AdmmCtl* ctl = nullptr, uint32_t q_off = 0, double inv_n = 0.0,

@@ -79,10 +79,12 @@ struct mvtv_problem {
     double* host_red = nullptr;   // pinned: reductions + PcgState mirror
     PcgState* host_st = nullptr;
     SpecPlan spec;                // spectral theta-solve tables (allocated when the mesh allows it)
-    bool spec_mesh = false;       // spectral solve: m_j <= 4096 for j < p - 1; the last dimension too on a slab rank
+    bool spec_mesh = false;       // spectral solve: every dimension j < p - 1 has a transform (m_j <= 4096, or a two-pass
+                                  // split); a slab rank: m_j <= 4096 for every j
+    int32_t split_forced[kMaxDims] = {0, 0, 0, 0};   // mvtv_problem_dct_split: the first factor per dimension, 0 automatic
     bool spec_long = false;       // ... with a last dimension longer than 4096 (the blocked line solve, spec.lb)
     bool spec_pow2 = false;       // ... and a power of two (k_dct8 / k_tri passes)
-    bool spec_lead = false;       // dims 0..p-2 are (the slab loop: the last dimension may have any length)
+    bool spec_lead = false;       // dims 0..p-2 have a transform (the slab loop: the last dimension may have any length)
     bool e3d = false;             // z-marching 3-D edge kernels
     bool f3d = false;             // fused 3-D edge update + gather (needs the second edge buffer)
     bool f4d = false;             // fused 4-D edge update + gather pass A (k_admm4a; second edge buffer, g4)

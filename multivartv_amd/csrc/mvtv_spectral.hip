@@ -1432,8 +1432,9 @@ __device__ __forceinline__ void mr_stage(double2* __restrict__ buf, const double
     __syncthreads();
 }
 
-template <bool DIF, bool INV>
-__device__ __forceinline__ void mr_fft(double2* buf, const double2* tw, int ncl, int m, int LP, const SpecArgs& a) {
+// (PL: SpecArgs, or a split pass's SubFft: nrad, rad, fper, fL of the length-m plan)
+template <bool DIF, bool INV, typename PL>
+__device__ __forceinline__ void mr_fft(double2* buf, const double2* tw, int ncl, int m, int LP, const PL& a) {
     auto stage = [&](int s, int L) {
         switch (a.rad[s]) {
             case 2: mr_stage<2, DIF, INV>(buf, tw, ncl, m, LP, L, a.fper[s], a.fL[s]); break;
@@ -5005,6 +5006,407 @@ static hipError_t launch_line_blocks(const SpecPlan& sp, const SpecArgs& a, hipS
     return hipGetLastError();
 }
 
+// =============================================================================================
+// A leading dimension longer than one workgroup's LDS (m > 4096), or any m = a b under mvtv_problem_dct_split: the
+// length-m complex FFT of the Makhoul pairing in two passes (the "four-step" factorisation). A line is an a x b matrix,
+// sample n = n1 b + n2, frequency k = k1 + a k2:
+//
+//   Z[k1 + a k2] = sum_n2 W_b^{n2 k2} ( W_m^{n2 k1} sum_n1 W_a^{n1 k1} v[n1 b + n2] )
+//
+// k_dsc (columns): length-a FFTs over n1 of a tile of columns n2 (the Makhoul order and b = in + ca ga + cb gb folded
+// into the load), times W_m^{n2 k1}, into the scratch as packed complex line pairs [pair][k1][n2]. k_dsr (rows):
+// length-b FFTs over n2 of rows k1 and a - k1 together, since Z[m - k] lives at (a - k1, b - 1 - k2) (row 0:
+// (0, b - k2)); Z[k], Z[m - k] -> the two lines' cosine coefficients as in k_dctg, stored at position b k1 + k2: the
+// frequencies stay in that order, the dimension's lam table is stored in it, and the inverse (k_dsr<INV> then
+// k_dsc<INV>) reads it back. Both run k_dctg's in-LDS stages (mr_fft, 512 threads).
+//
+// Twiddles. W_m^j, j < m and the quarter-wave e^{-i pi k/2m}, k < m are both powers of w = e^{-2 pi i/4m}: w^J =
+// T1[J >> 12] T2[J & 4095] with every entry a long-double value split into hi + lo doubles, the product formed with
+// its rounding errors carried, so a twiddle is as good as one rounded table entry at 32 B (4096 + m / 1024) of table
+// instead of 32 B m.
+namespace dsp {
+constexpr int SLOTS = spec::LDS_WORDS / 2 + 8 * spec::PAD;   // complex slots of a workgroup (64 KB and the pads)
+constexpr int GMAX = 64;                                     // row pairs per workgroup of the row pass
+}  // namespace dsp
+
+struct SubFft {
+    int32_t nrad;
+    int32_t rad[8];
+    FastDiv fper[8], fL[8];
+};
+
+struct SplitArgs {
+    const double* in;
+    const double* ga;
+    const double* gb;
+    double ca, cb;
+    double* out;
+    double2* scr;
+    const double2 *twa, *twb;
+    const double2 *t1, *t2;
+    const uint32_t *reva, *revb;
+    uint32_t m, a, b, stride, nlines, nclt;   // nclt: complex lines (line pairs)
+    uint32_t C, nct;                          // k_dsc: columns per workgroup, column tiles per line tile
+    uint32_t G, npr;                          // k_dsr: row pairs per workgroup, row pairs per line (a / 2 + 1)
+    int32_t tq;                               // k_dsc: real lines per workgroup
+    FastDiv fds, fC, fa, fb, fG, fnpr, fnclt, fnct;
+    const int32_t* skip;
+    const AdmmCtl* ctl;
+    SubFft pa, pb;
+};
+
+// w^J = T1[J >> 12] * T2[J & 4095], entries (re, im) hi then (re, im) lo
+__device__ __forceinline__ double2 dd_tw(const double2* __restrict__ t1, const double2* __restrict__ t2, uint32_t J) {
+#pragma clang fp contract(off)
+    const double2 uh = t1[2 * (J >> 12)], ul = t1[2 * (J >> 12) + 1];
+    const double2 vh = t2[2 * (J & 4095u)], vl = t2[2 * (J & 4095u) + 1];
+    auto two = [](double x, double y, double& e) {   // x + y = s + e
+        const double s = x + y, bb = s - x;
+        e = (x - (s - bb)) + (y - bb);
+        return s;
+    };
+    const double p1 = uh.x * vh.x, e1 = fma(uh.x, vh.x, -p1);
+    const double p2 = uh.y * vh.y, e2 = fma(uh.y, vh.y, -p2);
+    const double p3 = uh.x * vh.y, e3 = fma(uh.x, vh.y, -p3);
+    const double p4 = uh.y * vh.x, e4 = fma(uh.y, vh.x, -p4);
+    double er, ei;
+    const double re = two(p1, -p2, er), im = two(p3, p4, ei);
+    const double lr = er + (e1 - e2) + ((uh.x * vl.x + ul.x * vh.x) - (uh.y * vl.y + ul.y * vh.y));
+    const double li = ei + (e3 + e4) + ((uh.x * vl.y + ul.x * vh.y) + (uh.y * vl.x + ul.y * vh.x));
+    return make_double2(re + lr, im + li);
+}
+
+template <bool D0>
+__device__ __forceinline__ uint32_t dsp_addr(const SplitArgs& s, uint32_t q, uint32_t pos) {
+    if (D0) return q * s.m + pos;
+    const uint32_t hi = s.fds.div(q);
+    return (q - hi * s.stride) + hi * s.stride * s.m + pos * s.stride;
+}
+
+template <bool INV, bool D0, bool FORMB>
+__global__ __launch_bounds__(dctg::NT) void k_dsc(const SplitArgs s) {
+    double ca = s.ca, cb = s.cb;
+    if (s.skip && *s.skip) return;
+    if (s.ctl) {
+        if (s.ctl->done) return;
+        ca = s.ctl->rho;
+        cb = s.ctl->rho * s.ctl->c_prev;
+    }
+    extern __shared__ double2 buf[];   // (tq / 2) * C lines of a + PAD complex slots
+    const uint32_t a = s.a, b = s.b, m = s.m, C = s.C, tq = uint32_t(s.tq), ncl = tq >> 1;
+    const int LP = int(a) + spec::PAD;
+    const uint32_t lt = s.fnct.div(blockIdx.x), ct = blockIdx.x - lt * s.nct;
+    const uint32_t q0 = lt * tq, c0 = ct * C;
+    const uint32_t Ca = min(C, b - c0);   // this tile's columns
+    const int ltq = __ffs(int(tq)) - 1;
+    double* bw = reinterpret_cast<double*>(buf);
+    // real element e -> (line ql, column cc, row n1): lanes over the columns for d = 0, over the lines for d > 0
+    auto real_el = [&](uint32_t e, uint32_t& ql, uint32_t& cc, uint32_t& n1) {
+        if (D0) {
+            const uint32_t r = s.fC.div(e);
+            cc = e - r * C;
+            ql = s.fa.div(r);
+            n1 = r - ql * a;
+        } else {
+            ql = e & (tq - 1u);
+            const uint32_t r = e >> ltq;
+            n1 = s.fC.div(r);
+            cc = r - n1 * C;
+        }
+    };
+    // complex element e -> (complex line cl, column cc, row k1), lanes over the columns
+    auto cplx_el = [&](uint32_t e, uint32_t& cl, uint32_t& cc, uint32_t& k1) {
+        const uint32_t r = s.fC.div(e);
+        cc = e - r * C;
+        cl = s.fa.div(r);
+        k1 = r - cl * a;
+    };
+    const uint32_t nreal = tq * C * a, ncplx = ncl * C * a;
+
+    if (!INV) {
+        for (uint32_t e = threadIdx.x; e < nreal; e += dctg::NT) {
+            uint32_t ql, cc, n1;
+            real_el(e, ql, cc, n1);
+            double v = 0.0;
+            if (cc < Ca && q0 + ql < s.nlines) {
+                const uint32_t n = n1 * b + c0 + cc;
+                const uint32_t k = 2u * n < m ? 2u * n : 2u * (m - 1u - n) + 1u;   // v[n] = x[2n], v[m-1-n] = x[2n+1]
+                const uint32_t gi = dsp_addr<D0>(s, q0 + ql, k);
+                v = s.in[gi];
+                if (FORMB) v += ca * s.ga[gi] + cb * s.gb[gi];
+            }
+            bw[2 * (((ql >> 1) * C + cc) * LP + s.reva[n1]) + (ql & 1u)] = v;
+        }
+    } else {
+        for (uint32_t e = threadIdx.x; e < ncplx; e += dctg::NT) {
+            uint32_t cl, cc, k1;
+            cplx_el(e, cl, cc, k1);
+            const uint32_t c = (q0 >> 1) + cl;
+            double2 v = make_double2(0.0, 0.0);
+            if (cc < Ca && c < s.nclt)
+                v = cmul(s.scr[(c * a + k1) * b + c0 + cc], cconj(dd_tw(s.t1, s.t2, 4u * (c0 + cc) * k1)));
+            buf[(cl * C + cc) * LP + k1] = v;
+        }
+    }
+    __syncthreads();
+    if (!INV) mr_fft<false, false>(buf, s.twa, int(ncl * C), int(a), LP, s.pa);
+    else mr_fft<true, true>(buf, s.twa, int(ncl * C), int(a), LP, s.pa);
+    if (!INV) {
+        for (uint32_t e = threadIdx.x; e < ncplx; e += dctg::NT) {
+            uint32_t cl, cc, k1;
+            cplx_el(e, cl, cc, k1);
+            const uint32_t c = (q0 >> 1) + cl;
+            if (cc >= Ca || c >= s.nclt) continue;
+            s.scr[(c * a + k1) * b + c0 + cc] =
+                cmul(buf[(cl * C + cc) * LP + k1], dd_tw(s.t1, s.t2, 4u * (c0 + cc) * k1));
+        }
+    } else {
+        for (uint32_t e = threadIdx.x; e < nreal; e += dctg::NT) {
+            uint32_t ql, cc, n1;
+            real_el(e, ql, cc, n1);
+            if (cc >= Ca || q0 + ql >= s.nlines) continue;
+            const uint32_t n = n1 * b + c0 + cc;
+            const uint32_t k = 2u * n < m ? 2u * n : 2u * (m - 1u - n) + 1u;
+            s.out[dsp_addr<D0>(s, q0 + ql, k)] = bw[2 * (((ql >> 1) * C + cc) * LP + s.reva[n1]) + (ql & 1u)];
+        }
+    }
+}
+
+template <bool INV, bool D0>
+__global__ __launch_bounds__(dctg::NT) void k_dsr(const SplitArgs s) {
+    if (s.skip && *s.skip) return;
+    if (s.ctl && s.ctl->done) return;
+    extern __shared__ double2 buf[];   // 2 G lines (rows k1 and a - k1 of G row pairs) of b + PAD complex slots
+    const uint32_t a = s.a, b = s.b, G = s.G;
+    const int LP = int(b) + spec::PAD;
+    const uint32_t u0 = blockIdx.x * G, nU = s.nclt * s.npr;
+    // row pair g of this workgroup -> (complex line c, pair pr): pairs of a line adjacent for d = 0, lines adjacent
+    // for d > 0; false past the last one
+    auto unit = [&](uint32_t g, uint32_t& c, uint32_t& pr) {
+        const uint32_t u = u0 + g;
+        if (D0) {
+            c = s.fnpr.div(u);
+            pr = u - c * s.npr;
+        } else {
+            pr = s.fnclt.div(u);
+            c = u - pr * s.nclt;
+        }
+        return u < nU;
+    };
+    // LDS line fl = 2 g + which -> its row of the a x b matrix; false: no such line (past the end, or the pairs 0 and
+    // a / 2, which are one row)
+    auto line_row = [&](uint32_t fl, uint32_t& c, uint32_t& row) {
+        uint32_t pr;
+        const bool ok = unit(fl >> 1, c, pr);
+        row = (fl & 1u) ? a - pr : pr;
+        return ok && (!(fl & 1u) || (pr > 0u && 2u * pr != a));
+    };
+    // element e of the lines' global side -> (LDS line, position k2): lanes over k2 for d = 0, over the pairs for d > 0
+    auto glob_el = [&](uint32_t e, uint32_t& fl, uint32_t& k2) {
+        if (D0) {
+            fl = s.fb.div(e);
+            k2 = e - fl * b;
+        } else {
+            const uint32_t r = s.fG.div(e), g = e - r * G, w = s.fb.div(r);
+            k2 = r - w * b;
+            fl = 2u * g + w;
+        }
+    };
+    const uint32_t nel = 2u * G * b;
+
+    for (uint32_t e = threadIdx.x; e < nel; e += dctg::NT) {
+        uint32_t fl, k2, c, row;
+        double2 v = make_double2(0.0, 0.0);
+        if (!INV) {
+            fl = s.fb.div(e);
+            k2 = e - fl * b;
+            if (line_row(fl, c, row)) v = s.scr[(c * a + row) * b + k2];
+            buf[fl * LP + s.revb[k2]] = v;
+        } else {
+            glob_el(e, fl, k2);
+            if (line_row(fl, c, row)) {
+                v.x = s.in[dsp_addr<D0>(s, 2u * c, row * b + k2)];
+                if (2u * c + 1u < s.nlines) v.y = s.in[dsp_addr<D0>(s, 2u * c + 1u, row * b + k2)];
+            }
+            buf[fl * LP + k2] = v;
+        }
+    }
+    __syncthreads();
+    if (!INV) mr_fft<false, false>(buf, s.twb, int(2u * G), int(b), LP, s.pb);
+
+    // spectrum <-> cosine coefficients over the pairs (k, m - k), k = pr + a k2: the partner sits at (a - pr, b - 1 - k2),
+    // in the same row for the pairs 0 ((0, b - k2)) and a / 2; k = 0 and k = m / 2 pair with themselves
+    for (uint32_t t = threadIdx.x; t < G * b; t += dctg::NT) {
+        const uint32_t g = s.fb.div(t), k2 = t - g * b;
+        uint32_t c, pr;
+        if (!unit(g, c, pr)) continue;
+        const bool one_row = pr == 0u || 2u * pr == a;
+        const uint32_t k2p = pr == 0u ? (k2 ? b - k2 : 0u) : b - 1u - k2;
+        if (one_row && k2 > k2p) continue;
+        const bool self = one_row && k2 == k2p;
+        double2* xa = buf + (2u * g) * LP + k2;
+        double2* xb = buf + (2u * g + (one_row ? 0u : 1u)) * LP + k2p;
+        const uint32_t k = pr + a * k2;
+        const double2 q1 = dd_tw(s.t1, s.t2, k);            // e^{-i pi k / 2m}
+        const double2 q2 = make_double2(-q1.y, -q1.x);      // e^{-i pi (m - k) / 2m} = -i conj q1
+        if (!INV) {
+            const double2 Z1 = *xa;
+            if (self) {
+                *xa = make_double2(q1.x * Z1.x, q1.x * Z1.y);
+            } else {
+                const double2 Z2 = *xb;
+                const double2 Ap = make_double2(0.5 * (Z1.x + Z2.x), 0.5 * (Z1.y - Z2.y));
+                const double2 Bp = make_double2(0.5 * (Z1.y + Z2.y), -0.5 * (Z1.x - Z2.x));
+                *xa = make_double2(q1.x * Ap.x - q1.y * Ap.y, q1.x * Bp.x - q1.y * Bp.y);
+                *xb = make_double2(q2.x * Ap.x + q2.y * Ap.y, q2.x * Bp.x + q2.y * Bp.y);
+            }
+        } else {
+            // V[k] = conj(q[k]) (X[k] - i X[m-k]), X[m] = 0; Z = V_a + i V_b
+            const double2 Xk = *xa;
+            const double2 Xmk = self ? (k == 0u ? make_double2(0.0, 0.0) : Xk) : *xb;
+            const double2 q1c = cconj(q1), q2c = cconj(q2);
+            const double2 va1 = cmul(q1c, make_double2(Xk.x, -Xmk.x));
+            const double2 vb1 = cmul(q1c, make_double2(Xk.y, -Xmk.y));
+            *xa = make_double2(va1.x - vb1.y, va1.y + vb1.x);
+            if (!self) {
+                const double2 va2 = cmul(q2c, make_double2(Xmk.x, -Xk.x));
+                const double2 vb2 = cmul(q2c, make_double2(Xmk.y, -Xk.y));
+                *xb = make_double2(va2.x - vb2.y, va2.y + vb2.x);
+            }
+        }
+    }
+    __syncthreads();
+    if (INV) mr_fft<true, true>(buf, s.twb, int(2u * G), int(b), LP, s.pb);
+
+    for (uint32_t e = threadIdx.x; e < nel; e += dctg::NT) {
+        uint32_t fl, k2, c, row;
+        if (!INV) {
+            glob_el(e, fl, k2);
+            if (!line_row(fl, c, row)) continue;
+            const double2 v = buf[fl * LP + k2];
+            s.out[dsp_addr<D0>(s, 2u * c, row * b + k2)] = v.x;
+            if (2u * c + 1u < s.nlines) s.out[dsp_addr<D0>(s, 2u * c + 1u, row * b + k2)] = v.y;
+        } else {
+            fl = s.fb.div(e);
+            k2 = e - fl * b;
+            if (line_row(fl, c, row)) s.scr[(c * a + row) * b + k2] = buf[fl * LP + s.revb[k2]];
+        }
+    }
+}
+
+uint32_t dct_split_auto(uint32_t m) {
+    int rad[8], nrad = 0;
+    uint32_t best = 0;
+    for (uint32_t a = 2; uint64_t(a) * a <= m; ++a)
+        if (m % a == 0 && m / a <= kSplitMax && dct_radix_plan(a, rad, &nrad) && dct_radix_plan(m / a, rad, &nrad))
+            best = a;
+    return best;
+}
+
+static bool sub_fft_plan(uint32_t n, SubFft* f) {
+    if (!dct_radix_plan(n, f->rad, &f->nrad)) return false;
+    for (int st = 0, L = 1; st < f->nrad; ++st) {
+        f->fper[st] = FastDiv(n / uint32_t(f->rad[st]));
+        f->fL[st] = FastDiv(uint32_t(L));
+        L *= f->rad[st];
+    }
+    return true;
+}
+
+// the two launches of a split pass on s: forward k_dsc then k_dsr, inverse k_dsr<INV> then k_dsc<INV>. A timed pass
+// (g_timed) spans both: the start event on the first, the stop event on the second.
+static hipError_t launch_dct_split(const SpecPlan& sp, const Geom& g, hipStream_t st, int mode, int d, const double* in,
+                                   const double* ga, double ca, const double* gb, double cb, double* out,
+                                   const AdmmCtl* ctl, const int32_t* skip) {
+    const DctSplit& ds = sp.split[d];
+    const uint32_t m = g.m[d], a = ds.a, b = ds.b;
+    if (mode == SPEC_MID || d >= g.p - 1 || a < 2 || b < 2 || uint64_t(a) * b != m || a > kSplitMax || b > kSplitMax ||
+        !sp.stw || !sp.srev || !sp.sscr)
+        return hipErrorInvalidValue;
+    SplitArgs s{};
+    s.in = in;
+    s.ga = ga;
+    s.gb = gb;
+    s.ca = ca;
+    s.cb = cb;
+    s.out = out;
+    s.scr = reinterpret_cast<double2*>(sp.sscr);
+    s.twa = reinterpret_cast<const double2*>(sp.stw + ds.twa);
+    s.twb = reinterpret_cast<const double2*>(sp.stw + ds.twb);
+    s.t1 = reinterpret_cast<const double2*>(sp.stw + ds.t1);
+    s.t2 = reinterpret_cast<const double2*>(sp.stw + ds.t2);
+    s.reva = sp.srev + ds.reva;
+    s.revb = sp.srev + ds.revb;
+    s.m = m;
+    s.a = a;
+    s.b = b;
+    s.stride = g.stride[d];
+    s.nlines = g.N / m;
+    s.nclt = (s.nlines + 1u) / 2u;
+    if (2 * size_t(s.nclt) * m > sp.sscr_cap) return hipErrorInvalidValue;
+    s.skip = skip;
+    s.ctl = ctl;
+    if (!sub_fft_plan(a, &s.pa) || !sub_fft_plan(b, &s.pb)) return hipErrorInvalidValue;
+    const bool d0 = d == 0, formb = ga != nullptr, inv = mode == SPEC_INV;
+    if (formb && (inv || !gb)) return hipErrorInvalidValue;
+    // columns: 2 lines (d = 0) or <= 16 adjacent ones (128-B rows) by as many columns as the LDS holds, in even tiles
+    static const int slots_env = [] {   // probe builds: MVTV_DSP_SLOTS sizes both passes' tiles (complex LDS slots)
+        const char* e = probe_env("MVTV_DSP_SLOTS");
+        return e ? std::atoi(e) : 0;
+    }();
+    const uint32_t slots = slots_env > 0 ? uint32_t(slots_env) : uint32_t(dsp::SLOTS);
+    uint32_t tq = d0 ? 2u : 16u;
+    while (tq > 2u && (tq / 2u) * (a + 1u) > uint32_t(dsp::SLOTS)) tq /= 2u;
+    const uint32_t cmax = std::min(b, std::max(1u, slots / ((tq / 2u) * (a + 1u))));
+    s.tq = int(tq);
+    s.nct = (b + cmax - 1u) / cmax;
+    s.C = (b + s.nct - 1u) / s.nct;
+    // rows: as many row pairs as the LDS holds, <= GMAX
+    s.npr = a / 2u + 1u;
+    s.G = std::min<uint32_t>(uint32_t(dsp::GMAX), std::max(1u, slots / (2u * (b + 1u))));
+    s.fds = FastDiv(s.stride);
+    s.fC = FastDiv(s.C);
+    s.fa = FastDiv(a);
+    s.fb = FastDiv(b);
+    s.fG = FastDiv(s.G);
+    s.fnpr = FastDiv(s.npr);
+    s.fnclt = FastDiv(s.nclt);
+    s.fnct = FastDiv(s.nct);
+    const uint64_t gc = uint64_t((s.nlines + tq - 1u) / tq) * s.nct, gr = (uint64_t(s.nclt) * s.npr + s.G - 1u) / s.G;
+    if (gc > 0x7fffffffull || gr > 0x7fffffffull) return hipErrorInvalidValue;
+    const dim3 gridc{uint32_t(gc)}, gridr{uint32_t(gr)}, block(dctg::NT);
+    const size_t smc = size_t(tq / 2u) * s.C * (a + 1u) * sizeof(double2), smr = size_t(2u * s.G) * (b + 1u) * sizeof(double2);
+    const TimedLaunch tl = g_timed;
+    g_timed = TimedLaunch{};
+    auto go = [&](auto kern, dim3 grid, size_t smem, bool first) {
+        if (smem > 65536)
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      int(smem));
+        if (g_launch_log.on) launch_log_push(reinterpret_cast<const void*>(kern), grid, block);
+        hipEvent_t e0 = first ? tl.start : nullptr, e1 = first ? nullptr : tl.stop;
+        if (e0 || e1) hipExtLaunchKernelGGL(kern, grid, block, uint32_t(smem), st, e0, e1, 0u, s);
+        else hipLaunchKernelGGL(kern, grid, block, uint32_t(smem), st, s);
+    };
+    if (!inv) {
+        if (d0) {
+            if (formb) go(k_dsc<false, true, true>, gridc, smc, true);
+            else go(k_dsc<false, true, false>, gridc, smc, true);
+            go(k_dsr<false, true>, gridr, smr, false);
+        } else {
+            if (formb) go(k_dsc<false, false, true>, gridc, smc, true);
+            else go(k_dsc<false, false, false>, gridc, smc, true);
+            go(k_dsr<false, false>, gridr, smr, false);
+        }
+    } else if (d0) {
+        go(k_dsr<true, true>, gridr, smr, true);
+        go(k_dsc<true, true, false>, gridc, smc, false);
+    } else {
+        go(k_dsr<true, false>, gridr, smr, true);
+        go(k_dsc<true, false, false>, gridc, smc, false);
+    }
+    return hipGetLastError();
+}
+
 bool dct_pcg_fusable(const Geom& g, size_t partial_words) {
     const uint32_t m = g.m[0];
     if (g.p < 2 || m < 64 || m > 4096 || (m & (m - 1)) != 0 || probe_env("MVTV_DCT_LDS") || probe_env("MVTV_PCGS_NINE"))
@@ -5062,6 +5464,11 @@ hipError_t launch_dct_pass(const SpecPlan& sp, const Geom& g, hipStream_t s, int
     // the line solve along the last dimension in blocks: any length (mvtv_problem_line_blocks forces it at any m)
     if (sp.lb.nblk > 0 && mode == SPEC_MID && d == g.p - 1 && !fold && !(pf && pf->mode))
         return launch_line_blocks(sp, a, s, formb);
+    // a leading dimension in two passes: m > 4096 (the library's factorisation) or forced (mvtv_problem_dct_split)
+    if (d < g.p - 1 && sp.split[d].a > 0) {
+        if (fold || (pf && pf->mode)) return hipErrorInvalidValue;
+        return launch_dct_split(sp, g, s, mode, d, in, ga, ca, gb, cb, out, ctl, skip);
+    }
     if (m > 4096) return hipErrorInvalidValue;
     if (a.fold && (!formb || !gb || !ctl || (1u << a.L) != m || (1u << a.ls) != a.stride || a.L < 3 ||
                    probe_env("MVTV_DCT_LDS") || mode == SPEC_MID))
@@ -5083,7 +5490,7 @@ hipError_t launch_dct_pass(const SpecPlan& sp, const Geom& g, hipStream_t s, int
                 a.fL[st] = FastDiv(uint32_t(L));
                 L *= a.rad[st];
             }
-            a.perm = sp.perm + sp.lam_off[d];
+            a.perm = sp.perm + sp.perm_off[d];
         }
         static const bool few_off = probe_flag("MVTV_FEW_LINES_OFF");
         // strided passes: tiles in XCD runs (probe builds: MVTV_XRUN_OFF=1 deals them round-robin)
