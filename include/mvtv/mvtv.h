@@ -90,7 +90,8 @@ typedef enum mvtv_theta_solver {
     MVTV_SOLVER_SPECTRAL = 2,  /* direct: cosine transforms + a tridiagonal solve along the last dim. Exact for
                                   W = I (mesh == data) with, for j < p - 1, m_j <= 4096 (FFT plans for lengths with
                                   prime factors 2, 3, 5, 7, Bluestein's chirp-z for any other) or m_j = a * b with
-                                  both factors <= 4096 and 2-3-5-7-smooth (two passes, one GPU), and a last dimension
+                                  both factors <= 4096 and 2-3-5-7-smooth (two passes, one GPU), or any m_j under
+                                  mvtv_problem_dct_chirp (opt-in, one GPU), and a last dimension
                                   of any length (never transformed: a line solve, in blocks past 4096 rows);
                                   MVTV_BAD_ARG otherwise */
     MVTV_SOLVER_PCG_SPECTRAL = 3 /* PCG preconditioned by S (mean(W) I + sigma D^T D) S, its middle factor inverted
@@ -134,9 +135,9 @@ mvtv_status mvtv_problem_block_info(const mvtv_problem* prob, int32_t k, int32_t
 /* new O^T y and W for the same mesh (CV folds re-run create_cache_objects, rcpp…/solvers.cpp:347-348) */
 mvtv_status mvtv_problem_set_data(mvtv_problem* prob, const double* oty, const double* wdiag);
 /* 1 if MVTV_SOLVER_SPECTRAL applies to this problem (W = I; every m_j, j < p - 1, <= 4096 or, on one GPU, a product of
- * two 2-3-5-7-smooth factors <= 4096; the last dimension any length on one GPU), else 0. What stays refused: a leading
- * dimension above 4096 with a prime factor >= 11 (4099, 4100 = 2^2 5^2 41), and any dimension above 4096 on a slab
- * rank but the last of G >= 2. */
+ * two 2-3-5-7-smooth factors <= 4096; the last dimension any length on one GPU), else 0. What is refused by default: a
+ * leading dimension above 4096 with a prime factor >= 11 (4099, 4100 = 2^2 5^2 41), which mvtv_problem_dct_chirp or
+ * MVTV_DCT_CHIRP=1 switches on; what stays refused: any dimension above 4096 on a slab rank but the last of G >= 2. */
 int32_t mvtv_problem_spectral_ok(const mvtv_problem* prob);
 /* The line solve along the last dimension in `blocks` blocks [floor(m k / blocks), floor(m (k + 1) / blocks)) of every
  * line: per-block recursion sums, an interface step that gives every block its carries and closes the mirror, and a
@@ -157,6 +158,24 @@ mvtv_status mvtv_problem_line_blocks(mvtv_problem* prob, int32_t blocks);
  * rank, or a mesh the spectral solve does not accept. Waits for the problem's stream; (re)allocates the splits' tables
  * (32 B * (4096 + m_dim / 1024) + 20 B * (a + b) a dimension) and one scratch vector of <= N + m_dim doubles. */
 mvtv_status mvtv_problem_dct_split(mvtv_problem* prob, int32_t dim, int32_t a);
+/* Cosine transforms along dimension dim (< p - 1) by Bluestein's chirp-z identity with the length-M circular
+ * convolution, M = a * b >= 2 m_dim - 1, run as a two-pass FFT: any m_dim, so also a leading dimension above 4096 with
+ * a prime factor >= 11 (three launches a transform: columns in, fused rows, columns out). a = b = 0: off for that
+ * dimension (the default; a dimension that then has no transform makes the mesh refused again, and the scratch, the
+ * blocked line solve's and the line sweeps' buffers are released). a = -1 (b ignored): the library's M, the smallest 2-3-5-7-smooth M >= 2 m_dim - 1 with a factorisation into two factors <= 4096, a the
+ * largest such divisor <= sqrt(M). a, b >= 2: that M at any m_dim >= 2, both factors 2-3-5-7-smooth and <= 4096 (tests;
+ * the passes that rest under mvtv_problem_dct_split rest here too). The frequencies stay in natural order.
+ * MVTV_BAD_ARG for dim < 0 or >= p - 1, a factor above 4096 or with a prime factor >= 11, a * b < 2 m_dim - 1, a slab
+ * rank, a dimension with a forced mvtv_problem_dct_split (and dct_split(dim, a >= 2) on a dimension under chirp),
+ * a = -1 where no M exists (m_dim > (4096^2 + 1) / 2). Waits for the problem's stream, re-evaluates which solvers
+ * the mesh admits (mvtv_problem_spectral_ok, MVTV_SOLVER_AUTO) and (re)builds what a spectral problem owns: the tables
+ * (16 B * (2 m_dim + M) and the factor tables a dimension) and one scratch vector of 2 * ceil(lines / 2) * M doubles,
+ * about 2N; when that fails (MVTV_OUT_OF_MEMORY) the problem keeps the mode it had. The environment variable
+ * MVTV_DCT_CHIRP=1, read at problem creation, starts every leading dimension above 4096 without a two-pass
+ * factorisation (and with an M) in the automatic mode (not on a slab rank). */
+mvtv_status mvtv_problem_dct_chirp(mvtv_problem* prob, int32_t dim, int32_t a, int32_t b);
+/* the factors in use along dim (the automatic choice included); 0, 0: the dimension is not under chirp */
+mvtv_status mvtv_problem_dct_chirp_get(const mvtv_problem* prob, int32_t dim, int32_t* a, int32_t* b);
 /* The marching line sweeps of the 3-D spectral solve (m_1 = 512, m_0 a multiple of 16, one GPU): the dim-1 transforms
  * fused into the dim-2 line solve, two passes over the vector and an interface step over `chunks` chunks of dim 2 in
  * place of three passes. mode -1: automatic (the default: meshes of more than 2^24 nodes that fill the GPU with

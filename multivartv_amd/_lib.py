@@ -85,6 +85,8 @@ SIGNATURES = {
     "mvtv_problem_line_sweep": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "mvtv_problem_line_blocks": (C.c_int, [C.c_void_p, C.c_int32]),
     "mvtv_problem_dct_split": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "mvtv_problem_dct_chirp": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+    "mvtv_problem_dct_chirp_get": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mvtv_admm": (C.c_int, [C.c_void_p, C.POINTER(AdmmOpts), C.c_double, _dp, _dp, _dp, C.POINTER(AdmmStats)]),
     "mvtv_state_set": (C.c_int, [C.c_void_p, _dp, _dp, C.c_double]),
     "mvtv_state_get": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
@@ -386,6 +388,18 @@ class Problem:
         """The cosine transforms along dimension dim < p - 1 in two passes over m_dim = a * (m_dim / a): 0 automatic
         (only where m_dim > 4096), >= 2 that first factor at any m_dim (mvtv_problem_dct_split)."""
         _check(lib().mvtv_problem_dct_split(self._h, int(dim), int(a)))
+
+    def dct_chirp(self, dim, a=-1, b=0):
+        """Cosine transforms along dimension dim (< p - 1) by Bluestein's chirp-z identity over a two-pass convolution
+        of length M = a * b >= 2 m_dim - 1: any m_dim. a = -1 the library's M, a = b = 0 off (the default), a, b >= 2
+        those factors at any m_dim (mvtv_problem_dct_chirp). Re-evaluates spectral_ok()."""
+        _check(lib().mvtv_problem_dct_chirp(self._h, int(dim), int(a), int(b)))
+
+    def dct_chirp_factors(self, dim):
+        """(a, b) in use along dim, the automatic choice included; (0, 0): not under chirp."""
+        a, b = C.c_int32(0), C.c_int32(0)
+        _check(lib().mvtv_problem_dct_chirp_get(self._h, int(dim), C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
 
     def solve_spectral(self, sigma, b):
         bb = _f64(b, self.N)

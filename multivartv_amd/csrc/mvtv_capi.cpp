@@ -576,6 +576,76 @@ mvtv_status line_blocks_setup(mvtv_problem* P, int blocks) {
     return MVTV_OK;
 }
 
+// DFT of any 2-3-5-7-smooth length (sign -1, unnormalised) in long double, decimation in time over the smallest prime
+// first; w: the M twiddles e^{-2 pi i k/M} from exact angles. out and in do not overlap.
+void fft_smooth_ld(const std::complex<long double>* in, size_t stride, size_t n, std::complex<long double>* out,
+                   const std::vector<std::complex<long double>>& w) {
+    if (n == 1) {
+        out[0] = in[0];
+        return;
+    }
+    const size_t M = w.size();
+    size_t r = 7;
+    for (size_t q : {2, 3, 5})
+        if (n % q == 0) {
+            r = q;
+            break;
+        }
+    const size_t sub = n / r;
+    for (size_t q = 0; q < r; ++q) fft_smooth_ld(in + q * stride, stride * r, sub, out + q * sub, w);
+    std::complex<long double> t[7];
+    for (size_t k = 0; k < sub; ++k) {
+        for (size_t q = 0; q < r; ++q) t[q] = out[q * sub + k] * w[(q * k * (M / n)) % M];
+        for (size_t pp = 0; pp < r; ++pp) {
+            std::complex<long double> acc = t[0];
+            for (size_t q = 1; q < r; ++q) acc += t[q] * w[((q * pp) % r) * (M / r)];
+            out[k + pp * sub] = acc;
+        }
+    }
+}
+
+// Tables of one chirp dimension, appended to tw at dc's offsets: the chirp c[n] = e^{-i pi n^2/m} (n^2 mod 2m exactly),
+// the quarter wave e^{-i pi k/2m}, and H = FFT_M(h) / M of h[j] = conj c[|j|] wrapped to M = a b, stored where the
+// row pass meets frequency k1 + a k2: position b k1 + k2. h is symmetric, so the inverse transform (taken as the
+// conjugate of a forward one) reads the same H.
+void chirp_tables(uint32_t m, uint32_t a, uint32_t b, DctChirp* dc, std::vector<double>& tw) {
+    const long double pi = 3.141592653589793238462643383279502884L;
+    const size_t M = size_t(a) * b;
+    std::vector<std::complex<long double>> c(m), h(M, 0.0L), Hh(M), w(M);
+    for (uint32_t n = 0; n < m; ++n) {
+        const uint64_t r = (uint64_t(n) * n) % (2 * uint64_t(m));
+        const long double ang = -pi * (long double)r / (long double)m;
+        c[n] = std::complex<long double>(cosl(ang), sinl(ang));
+    }
+    for (size_t k = 0; k < M; ++k) {
+        const long double ang = -2.0L * pi * (long double)k / (long double)M;
+        w[k] = std::complex<long double>(cosl(ang), sinl(ang));
+    }
+    for (uint32_t j = 0; j < m; ++j) {
+        h[j] = std::conj(c[j]);
+        if (j > 0) h[M - j] = std::conj(c[j]);
+    }
+    fft_smooth_ld(h.data(), 1, M, Hh.data(), w);
+    dc->chirp = uint32_t(tw.size());
+    for (uint32_t n = 0; n < m; ++n) {
+        tw.push_back(double(c[n].real()));
+        tw.push_back(double(c[n].imag()));
+    }
+    dc->qw = uint32_t(tw.size());
+    for (uint32_t k = 0; k < m; ++k) {
+        const long double ang = -pi * k / (2.0L * m);
+        tw.push_back(double(cosl(ang)));
+        tw.push_back(double(sinl(ang)));
+    }
+    dc->H = uint32_t(tw.size());
+    for (uint32_t k1 = 0; k1 < a; ++k1)
+        for (uint32_t k2 = 0; k2 < b; ++k2) {
+            const std::complex<long double> v = Hh[k1 + size_t(a) * k2] / (long double)M;
+            tw.push_back(double(v.real()));
+            tw.push_back(double(v.imag()));
+        }
+}
+
 // a factor of a split: 2 <= n <= 4096 with a 2-3-5-7 plan
 bool split_factor_ok(uint32_t n) {
     int rad[8], nrad = 0;
@@ -630,6 +700,31 @@ mvtv_status dct_split_setup(mvtv_problem* P) {
         const uint32_t m = P->g.m[j];
         DctSplit& ds = sp.split[j];
         ds = DctSplit{};
+        DctChirp& dc = sp.chirp[j];
+        dc = DctChirp{};
+        if (P->chirp_forced[j][0] != 0) {   // the chirp-z transform: natural frequency order, its own tables
+            std::vector<double> lam(m);
+            for (uint32_t k = 0; k < m; ++k) {
+                const long double sn = sinl(pi * k / (2.0L * m));
+                lam[k] = double(4.0L * sn * sn);
+            }
+            HIP_TRY(hipMemcpy(sp.lam + sp.lam_off[j], lam.data(), size_t(m) * sizeof(double), hipMemcpyHostToDevice));
+            uint32_t ca = uint32_t(P->chirp_forced[j][0]), cb = uint32_t(P->chirp_forced[j][1]);
+            if (P->chirp_forced[j][0] < 0 && !dct_chirp_auto(m, &ca, &cb))
+                return fail(MVTV_BAD_ARG, "dct_chirp: no convolution length");
+            dc.a = ca;
+            dc.b = cb;
+            const uint64_t M = uint64_t(ca) * cb;
+            fft_tables(dc.a, &dc.twa, &dc.reva);
+            fft_tables(dc.b, &dc.twb, &dc.revb);
+            dc.t1 = uint32_t(tw.size());
+            for (uint64_t i = 0; i * 4096 < M; ++i) hilo(i * 4096, M);
+            dc.t2 = uint32_t(tw.size());
+            for (uint64_t i = 0; i < 4096; ++i) hilo(i, M);
+            chirp_tables(m, ca, cb, &dc, tw);
+            scratch = std::max(scratch, 2 * ((size_t(P->g.N / m) + 1) / 2) * size_t(M));
+            continue;
+        }
         const uint32_t a = P->split_forced[j] ? uint32_t(P->split_forced[j]) : (m > kSplitMax ? dct_split_auto(m) : 0u);
         if (m > kSplitMax && a == 0) return fail(MVTV_BAD_ARG, "dct_split: no factorisation");
         std::vector<double> lam(m);
@@ -669,11 +764,89 @@ mvtv_status dct_split_setup(mvtv_problem* P) {
     return MVTV_OK;
 }
 
-// a leading dimension runs in two passes: the passes that hold a whole line of it in one workgroup rest
+// a leading dimension runs in two passes (or the chirp transform's three): the passes that hold a whole line of it in
+// one workgroup rest
 bool split_on(const mvtv_problem* P) {
     for (int j = 0; j < P->g.p - 1; ++j)
-        if (P->spec.split[j].a > 0) return true;
+        if (P->spec.split[j].a > 0 || P->spec.chirp[j].a > 0) return true;
     return false;
+}
+
+// Which meshes the spectral solve takes. Cosine transforms of any length <= 4096: FFT plans for 2-3-5-7 lengths,
+// Bluestein (k_dctb) for the rest; a longer leading dimension with a factorisation a * b, both 2-3-5-7-smooth and
+// <= 4096, in two passes, and any leading dimension under mvtv_problem_dct_chirp (dct_split_setup). The last dimension
+// is never transformed: on one GPU it may have any length (spec_long: the blocked line solve); a slab rank keeps the
+// old rule for every dimension (its loop has the substructured solve over the ranks)
+void spectral_gate(mvtv_problem* P) {
+    const int p = P->g.p;
+    P->spec_mesh = P->spec_pow2 = P->spec_lead = true;
+    P->spec_long = false;
+    for (int j = 0; j < p; ++j) {
+        const uint32_t mj = (P->slab && j == p - 1) ? uint32_t(P->m_global) : P->g.m[j];
+        if (mj > 4096) {
+            const bool split = j < p - 1 && !P->slab && (P->chirp_forced[j][0] != 0 || dct_split_auto(mj) != 0);
+            if (j < p - 1 && !split) P->spec_lead = false;
+            if (j == p - 1 && !P->slab) P->spec_long = true;
+            else if (!split) P->spec_mesh = false;
+        }
+        if ((mj & (mj - 1)) != 0) P->spec_pow2 = false;
+    }
+    if (!P->spec_mesh) P->spec_long = false;
+    if (!P->spec_mesh || P->spec_long) P->spec_pow2 = false;
+}
+
+// Everything a spectral mesh owns, in order: the resident tables (once; they depend on the mesh alone), the marching
+// line sweeps' gate (MVTV_LINE_SWEEP=0 off), the blocked last-dimension solve where that dimension is long, the
+// two-pass and chirp transforms' tables and scratch. Shared by problem creation and mvtv_problem_dct_chirp, which can
+// make a refused mesh spectral later.
+mvtv_status spectral_setup(mvtv_problem* P) {
+    const int p = P->g.p;
+    const bool first = !P->spec.tw;
+    if (first && (P->spec_mesh || (P->slab && P->spec_lead && p >= 2))) MVTV_TRY(spectral_plan(P));
+    if (first && P->spec_mesh && !P->slab) {
+        const char* e = std::getenv("MVTV_LINE_SWEEP");
+        MVTV_TRY(line_sweep_setup(P, (e && std::atoi(e) == 0) ? 0 : -1, 0));
+    }
+    if (P->spec_long && P->spec.lb.nblk == 0) MVTV_TRY(line_blocks_setup(P, 0));
+    if (P->spec_mesh && !P->slab) MVTV_TRY(dct_split_setup(P));
+    return MVTV_OK;
+}
+
+// a captured loop (probe builds) holds the launches of the transforms it was captured with: dct_split and dct_chirp
+// change them without changing any buffer of the graph's key
+void drop_graphs(mvtv_problem* P) {
+    for (auto& lg : P->graphs)
+        if (lg.exec) (void)hipGraphExecDestroy(lg.exec);
+    P->graphs.clear();
+}
+
+// a mesh that is refused (again): no transform is in use, and what the spectral period allocated beyond the mesh's
+// own resident tables goes back: the transforms' scratch, the blocked line solve's and the line sweeps' buffers (which
+// mvtv_problem_line_blocks / _line_sweep could no longer reach on a refused mesh)
+void spectral_release(mvtv_problem* P) {
+    SpecPlan& sp = P->spec;
+    for (int j = 0; j < kMaxDims; ++j) {
+        sp.split[j] = DctSplit{};
+        sp.chirp[j] = DctChirp{};
+    }
+    for (double** b : {&sp.sscr, &sp.lb_coef, &sp.lb_lr, &P->ls_coef, &P->ls_lr})
+        if (*b) {
+            (void)hipFree(*b);
+            *b = nullptr;
+        }
+    sp.sscr_cap = 0;
+    sp.lb_cap = 0;
+    sp.lb = LineBlocks{};
+    P->ls_cap = 0;
+    P->ls_chunks = 0;
+}
+
+// the mesh gate for the current chirp_forced / split_forced, and what follows from it
+mvtv_status chirp_apply(mvtv_problem* P) {
+    spectral_gate(P);
+    if (P->spec_mesh) return spectral_setup(P);
+    spectral_release(P);
+    return MVTV_OK;
 }
 
 bool sweeps_on(const mvtv_problem* P) { return P->ls_chunks > 0 && P->spec.lb.nblk == 0 && !split_on(P); }
@@ -1111,33 +1284,18 @@ mvtv_status problem_create_impl(const mvtv_problem_desc* d, const mvtv_slab_desc
         return s;
     }
     P->host_st = reinterpret_cast<PcgState*>(P->host_red + 16);
-    // cosine transforms of any length <= 4096: FFT plans for 2-3-5-7 lengths, Bluestein (k_dctb) for the rest; a longer
-    // leading dimension with a factorisation a * b, both 2-3-5-7-smooth and <= 4096, in two passes (dct_split_setup).
-    // The last dimension is never transformed: on one GPU it may have any length (spec_long: the blocked line solve); a
-    // slab rank keeps the old rule for every dimension (its loop has the substructured solve over the ranks)
-    P->spec_mesh = P->spec_pow2 = P->spec_lead = true;
-    P->spec_long = false;
-    for (int j = 0; j < p; ++j) {
-        const uint32_t mj = uint32_t(mg[j]);
-        if (mj > 4096) {
-            const bool split = j < p - 1 && !P->slab && dct_split_auto(mj) != 0;
-            if (j < p - 1 && !split) P->spec_lead = false;
-            if (j == p - 1 && !P->slab) P->spec_long = true;
-            else if (!split) P->spec_mesh = false;
+    // MVTV_DCT_CHIRP=1: every leading dimension above 4096 without a two-pass factorisation starts under the chirp
+    // transform with the library's convolution length (not on a slab rank); unset or 0: such a mesh is refused
+    if (const char* e = std::getenv("MVTV_DCT_CHIRP"); e && std::atoi(e) != 0 && !P->slab)
+        for (int j = 0; j < p - 1; ++j) {
+            uint32_t ca = 0, cb = 0;
+            if (g.m[j] > kSplitMax && dct_split_auto(g.m[j]) == 0 && dct_chirp_auto(g.m[j], &ca, &cb))
+                P->chirp_forced[j][0] = -1;
         }
-        if ((mj & (mj - 1)) != 0) P->spec_pow2 = false;
-    }
-    if (!P->spec_mesh) P->spec_long = false;
-    if (!P->spec_mesh || P->spec_long) P->spec_pow2 = false;
-    // a slab problem's last dimension is solved by the substructured line solves (any length): the tables
-    // are needed for the transforms along dims 0..p-2 only
-    if (P->spec_mesh || (P->slab && P->spec_lead && p >= 2)) s = spectral_plan(P);
-    if (s == MVTV_OK && P->spec_mesh && !P->slab) {   // the marching line sweeps: the gate, MVTV_LINE_SWEEP=0 off
-        const char* e = std::getenv("MVTV_LINE_SWEEP");
-        s = line_sweep_setup(P, (e && std::atoi(e) == 0) ? 0 : -1, 0);
-    }
-    if (s == MVTV_OK && P->spec_long) s = line_blocks_setup(P, 0);
-    if (s == MVTV_OK && P->spec_mesh && !P->slab) s = dct_split_setup(P);
+    // which meshes the spectral solve takes, and what such a problem owns (a slab problem's last dimension is solved
+    // by the substructured line solves, any length: its tables are needed for the transforms along dims 0..p-2 only)
+    spectral_gate(P);
+    s = spectral_setup(P);
     P->e3d = edge3d_ok(g);
     if (s == MVTV_OK && P->e3d && g.p == 4 && gather4_ok(g)) s = alloc(&P->g4, 4 * size_t(N));
     P->f3d = fused3d_ok(g);   // slab problems too: the fused pass runs on the owned planes (Geom.ibeg/iend)
@@ -1210,8 +1368,53 @@ mvtv_status mvtv_problem_dct_split(mvtv_problem* P, int32_t dim, int32_t a) {
     if (a != 0 && (a < 2 || uint32_t(a) >= m || m % uint32_t(a) != 0 || !split_factor_ok(uint32_t(a)) ||
                    !split_factor_ok(m / uint32_t(a))))
         return fail(MVTV_BAD_ARG, "dct_split: a = 0, or m_dim = a * b with both factors 2-3-5-7-smooth in [2, 4096]");
+    if (a != 0 && P->chirp_forced[dim][0] != 0)
+        return fail(MVTV_BAD_ARG, "dct_split: the dimension is under dct_chirp");
     P->split_forced[dim] = a;
+    drop_graphs(P);
     return dct_split_setup(P);
+}
+
+mvtv_status mvtv_problem_dct_chirp(mvtv_problem* P, int32_t dim, int32_t a, int32_t b) {
+    if (!P) return fail(MVTV_BAD_ARG, "null problem");
+    DeviceGuard dg(P->device);
+    if (P->slab) return fail(MVTV_BAD_ARG, "dct_chirp: not a slab rank");
+    if (dim < 0 || dim >= P->g.p - 1) return fail(MVTV_BAD_ARG, "dct_chirp: 0 <= dim < p - 1");
+    const uint32_t m = P->g.m[dim];
+    if (a == -1) {
+        uint32_t ca = 0, cb = 0;
+        if (!dct_chirp_auto(m, &ca, &cb)) return fail(MVTV_BAD_ARG, "dct_chirp: no convolution length for this m");
+        b = 0;
+    } else if (a != 0 || b != 0) {
+        if (a < 2 || b < 2 || !split_factor_ok(uint32_t(a)) || !split_factor_ok(uint32_t(b)) ||
+            uint64_t(a) * uint64_t(b) + 1 < 2 * uint64_t(m))
+            return fail(MVTV_BAD_ARG,
+                        "dct_chirp: a = b = 0, a = -1, or a * b >= 2 m_dim - 1 with both factors 2-3-5-7-smooth in [2, 4096]");
+    }
+    if (a != 0 && P->split_forced[dim] != 0)
+        return fail(MVTV_BAD_ARG, "dct_chirp: the dimension has a forced dct_split");
+    HIP_TRY(hipStreamSynchronize(P->stream));
+    const int32_t old_a = P->chirp_forced[dim][0], old_b = P->chirp_forced[dim][1];
+    P->chirp_forced[dim][0] = a;
+    P->chirp_forced[dim][1] = b;
+    drop_graphs(P);
+    const mvtv_status s = chirp_apply(P);
+    if (s != MVTV_OK) {   // e.g. no memory for the ~2N scratch: back to the mode before the call
+        P->chirp_forced[dim][0] = old_a;
+        P->chirp_forced[dim][1] = old_b;
+        if (chirp_apply(P) != MVTV_OK) {   // nor for that one: nothing spectral stays in use (Jacobi-PCG)
+            P->spec_mesh = P->spec_long = P->spec_pow2 = false;
+            spectral_release(P);
+        }
+    }
+    return s;
+}
+
+mvtv_status mvtv_problem_dct_chirp_get(const mvtv_problem* P, int32_t dim, int32_t* a, int32_t* b) {
+    if (!P || dim < 0 || dim >= P->g.p - 1) return fail(MVTV_BAD_ARG, "dct_chirp_get: 0 <= dim < p - 1");
+    if (a) *a = int32_t(P->spec.chirp[dim].a);
+    if (b) *b = int32_t(P->spec.chirp[dim].b);
+    return MVTV_OK;
 }
 
 mvtv_status mvtv_problem_block_info(const mvtv_problem* P, int32_t k, int32_t* code, int32_t* sprime, double* weight) {

@@ -20,7 +20,8 @@ namespace mvtv {
 // Experiment knobs (tile shapes, buffer placement probes, alternative kernels) are read from the
 // environment only in a probe build (`make PROBES=1`, -DMVTV_PROBES); the release library always
 // takes the defaults. The run-time options a user may set are MVTV_ZPICK=0 (keep the allocation-order
-// z buffer pair), MVTV_LINE_SWEEP=0 (the 3-D solve's marching line sweeps off), MVTV_ADMM_SYNC=1
+// z buffer pair), MVTV_LINE_SWEEP=0 (the 3-D solve's marching line sweeps off), MVTV_DCT_CHIRP=1 (the chirp transform
+// on for every leading dimension above 4096 without a two-pass factorisation), MVTV_ADMM_SYNC=1
 // (host-synchronous ADMM loop) and MVTV_PCG=classic (3-kernel PCG).
 inline const char* probe_env(const char* name) {
 #ifdef MVTV_PROBES
@@ -319,9 +320,27 @@ struct DctSplit {
 constexpr uint32_t kSplitMax = 4096;   // the longest factor (and the longest resident line)
 // the library's factorisation of a 2-3-5-7-smooth m: the largest a <= sqrt(m) with m / a <= kSplitMax; 0: none
 uint32_t dct_split_auto(uint32_t m);
+// The chirp-z cosine transform of a leading dimension of any length m (k_chc, k_chr, k_cho; mvtv_problem_dct_chirp):
+// the length-M circular convolution of Bluestein's identity, M = a * b >= 2m - 1, as a two-pass FFT. a = 0: off.
+// Offsets into SpecPlan::stw (doubles) and SpecPlan::srev.
+struct DctChirp {
+    uint32_t a = 0, b = 0;
+    uint32_t twa = 0, twb = 0;     // a / b complex FFT twiddles
+    uint32_t t1 = 0, t2 = 0;       // e^{-2 pi i J/M} as hi + lo pairs: T1[J >> 12] * T2[J & 4095]
+    uint32_t chirp = 0, qw = 0;    // m complex values each: e^{-i pi n^2/m}; e^{-i pi k/2m}
+    uint32_t H = 0;                // M complex values: FFT_M(h) / M, h[j] = conj c[|j|] wrapped, at position b k1 + k2
+                                   // for frequency k1 + a k2
+    uint32_t reva = 0, revb = 0;
+};
+// the library's M = a b for length m: the smallest 2-3-5-7-smooth M >= 2m - 1 with both factors <= kSplitMax, a the
+// largest such divisor <= sqrt(M); false: none
+bool dct_chirp_auto(uint32_t m, uint32_t* a, uint32_t* b);
 // Spectral theta-solve tables (mvtv_spectral.hip), device-resident, offsets in doubles.
 struct SpecPlan {
     DctSplit split[kMaxDims];
+    // chirp dimensions share stw / srev and the scratch: 2 ceil(lines / 2) M doubles for a chirp dimension (the
+    // packed line pairs' length-M spectra, about 2N), against N + m for a split one
+    DctChirp chirp[kMaxDims];
     double* stw = nullptr;       // the splits' twiddle tables
     uint32_t* srev = nullptr;
     double* sscr = nullptr;      // the splits' scratch between their two passes: sscr_cap doubles (<= N + m_j)
@@ -394,7 +413,9 @@ bool dct_radix_plan(uint32_t m, int* rad, int* nrad);
 // ga != nullptr forms the input as in + ca*ga + cb*gb. In place (in == out) is allowed. m_d <= 4096, except mode 2
 // along d = p - 1 while sp.lb.nblk > 0: the blocked line solve (three launches; p = 1: 16-B aligned arrays), and modes
 // 0 / 1 along a dimension with sp.split[d].a > 0: the two-pass transform (two launches through sp.sscr; its
-// frequencies stay in the order position b k1 + k2 <-> k = k1 + a k2, the order of that dimension's lam table).
+// frequencies stay in the order position b k1 + k2 <-> k = k1 + a k2, the order of that dimension's lam table), and
+// modes 0 / 1 along a dimension with sp.chirp[d].a > 0: the chirp transform (three launches through sp.sscr, natural
+// frequency order).
 hipError_t launch_dct_pass(const SpecPlan& sp, const Geom& g, hipStream_t s, int mode, int d, const double* in,
                            const double* ga, double ca, const double* gb, double cb, double* out, double sigma,
                            double w0, const AdmmCtl* ctl = nullptr, uint32_t q_off = 0, double inv_n = 0.0,

@@ -82,6 +82,8 @@ struct mvtv_problem {
     bool spec_mesh = false;       // spectral solve: every dimension j < p - 1 has a transform (m_j <= 4096, or a two-pass
                                   // split); a slab rank: m_j <= 4096 for every j
     int32_t split_forced[kMaxDims] = {0, 0, 0, 0};   // mvtv_problem_dct_split: the first factor per dimension, 0 automatic
+    // mvtv_problem_dct_chirp: the convolution's factors (a, b) per dimension; a = -1 the library's, 0 off
+    int32_t chirp_forced[kMaxDims][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};
     bool spec_long = false;       // ... with a last dimension longer than 4096 (the blocked line solve, spec.lb)
     bool spec_pow2 = false;       // ... and a power of two (k_dct8 / k_tri passes)
     bool spec_lead = false;       // dims 0..p-2 have a transform (the slab loop: the last dimension may have any length)

@@ -5407,6 +5407,360 @@ static hipError_t launch_dct_split(const SpecPlan& sp, const Geom& g, hipStream_
     return hipGetLastError();
 }
 
+// =============================================================================================
+// A leading dimension under mvtv_problem_dct_chirp (any m, so also m > 4096 with a prime factor >= 11): the length-m
+// complex DFT of the Makhoul pairing by Bluestein's identity n k = (n^2 + k^2 - (k - n)^2) / 2,
+//
+//   Z[k] = c[k] sum_n (v[n] c[n]) conj c[k - n],   c[n] = e^{-i pi n^2 / m},
+//
+// a circular convolution of length M = a b >= 2m - 1 taken as a two-pass FFT (sample n = n1 b + n2, frequency
+// k1 + a k2 of the length-M transform, as in the split passes above). Three launches, one round trip of the scratch
+// [pair][k1][n2] between each:
+//
+//   k_chc (columns in):  load (the Makhoul order and b = in + ca ga + cb gb folded in), times c[n], zero for n >= m,
+//                        length-a FFTs over n1, times W_M^{n2 k1}
+//   k_chr (rows):        per row k1 the length-b FFT, times the filter spectrum H at (k1, k2) (stored in that order, so
+//                        no transposition exists), the inverse length-b FFT, times conj W_M^{n2 k1}, in place
+//   k_cho (columns out): inverse length-a FFTs, n < m kept, times c[n]; Z[k] and Z[m - k] -> the two lines' cosine
+//                        coefficients at their natural position k
+//
+// Z[m - k] of k = n1 b + n2 sits in column (m - n2) mod b whatever n1, so a column tile is a set of orbits of that
+// involution (chirp_orbit) and a workgroup of k_cho holds both partners: no fourth pass, no complex spectrum written
+// out. All three kernels tile by orbits, so one index rule serves them. The inverse cosine transform is the same
+// three launches: the inverse DFT is conj(DFT(conj V)), V[k] = conj q[k] (X[k] - i X[m - k]) gathered on k_chc's load,
+// the real lines stored by k_cho in the Makhoul order; the filter h[j] = conj c[|j|] is symmetric, so one H serves both.
+// The frequencies come out in natural order: the dimension's lam table is the natural one.
+struct ChirpArgs {
+    const double* in;
+    const double* ga;
+    const double* gb;
+    double ca, cb;
+    double* out;
+    double2* scr;
+    const double2 *twa, *twb;   // the factor FFTs' twiddles
+    const double2 *t1, *t2;     // W_M^J = T1[J >> 12] T2[J & 4095], hi + lo entries (dd_tw)
+    const double2 *chirp, *qw;  // c[n], n < m; e^{-i pi k / 2m}, k < m
+    const double2* H;           // FFT_M(h) / M at position b k1 + k2 for frequency k1 + a k2
+    const uint32_t *reva, *revb;
+    uint32_t m, a, b, stride, nlines, nclt;
+    uint32_t r, nlo, norb;      // m mod b; orbits (t, r - t), t < nlo = r / 2 + 1; then (r + 1 + t - nlo, b - 1 - (t - nlo))
+    uint32_t Ch, nct;           // orbits per workgroup (2 Ch column slots), column tiles per line tile
+    uint32_t G;                 // k_chr: rows per workgroup
+    int32_t tq;                 // real lines per workgroup of the column passes
+    FastDiv fds, fC, fa, fb;
+    FastDiv fnct;
+    const int32_t* skip;
+    const AdmmCtl* ctl;
+    SubFft pa, pb;
+};
+
+// column of slot cc of the tile starting at orbit t0: the orbits' first columns in slots [0, Ch), their partners in
+// [Ch, 2 Ch); false for a slot past the last orbit or the second slot of a fixed point
+__device__ __forceinline__ bool chirp_col(const ChirpArgs& s, uint32_t t0, uint32_t cc, uint32_t& col) {
+    const bool second = cc >= s.Ch;
+    const uint32_t t = t0 + (second ? cc - s.Ch : cc);
+    if (t >= s.norb) return false;
+    uint32_t u, up;
+    if (t < s.nlo) {
+        u = t;
+        up = s.r - t;
+    } else {
+        u = s.r + 1u + (t - s.nlo);
+        up = s.b - 1u - (t - s.nlo);
+    }
+    col = second ? up : u;
+    return !second || up != u;
+}
+
+template <bool D0>
+__device__ __forceinline__ uint32_t chirp_addr(const ChirpArgs& s, uint32_t q, uint32_t pos) {
+    if (D0) return q * s.m + pos;
+    const uint32_t hi = s.fds.div(q);
+    return (q - hi * s.stride) + hi * s.stride * s.m + pos * s.stride;
+}
+
+// element e of a column tile -> (complex line cl, slot cc, row): the scratch side has the lanes over the columns; the
+// global side too for d = 0, over the adjacent lines for d > 0
+template <bool LINES>
+__device__ __forceinline__ void chirp_el(const ChirpArgs& s, uint32_t e, uint32_t ncl, uint32_t& cl, uint32_t& cc,
+                                         uint32_t& row) {
+    const uint32_t C = 2u * s.Ch;
+    if (!LINES) {
+        const uint32_t r = s.fC.div(e);
+        cc = e - r * C;
+        cl = s.fa.div(r);
+        row = r - cl * s.a;
+    } else {
+        cl = e & (ncl - 1u);   // ncl a power of two
+        const uint32_t r = e >> (__ffs(int(ncl)) - 1);
+        row = s.fC.div(r);
+        cc = r - row * C;
+    }
+}
+
+template <bool INV, bool D0, bool FORMB>
+__global__ __launch_bounds__(dctg::NT) void k_chc(const ChirpArgs s) {
+    double ca = s.ca, cb = s.cb;
+    if (s.skip && *s.skip) return;
+    if (s.ctl) {
+        if (s.ctl->done) return;
+        ca = s.ctl->rho;
+        cb = s.ctl->rho * s.ctl->c_prev;
+    }
+    extern __shared__ double2 buf[];   // (tq / 2) * 2 Ch lines of a + PAD complex slots
+    const uint32_t a = s.a, b = s.b, m = s.m, C = 2u * s.Ch, ncl = uint32_t(s.tq) >> 1;
+    const int LP = int(a) + spec::PAD;
+    const uint32_t lt = s.fnct.div(blockIdx.x), ct = blockIdx.x - lt * s.nct;
+    const uint32_t c0 = lt * ncl, t0 = ct * s.Ch;
+    const uint32_t nel = ncl * C * a;
+
+    for (uint32_t e = threadIdx.x; e < nel; e += dctg::NT) {
+        uint32_t cl, cc, n1, col = 0;
+        chirp_el<!D0>(s, e, ncl, cl, cc, n1);
+        const bool live = chirp_col(s, t0, cc, col);
+        const uint32_t c = c0 + cl, n = n1 * b + col;
+        double2 v = make_double2(0.0, 0.0);
+        if (live && c < s.nclt && n < m) {   // (rows n1 >= ceil(m / b) are zero padding: nothing to load)
+            const bool two = 2u * c + 1u < s.nlines;
+            if (!INV) {
+                const uint32_t k = 2u * n < m ? 2u * n : 2u * (m - 1u - n) + 1u;   // v[n] = x[2n], v[m-1-n] = x[2n+1]
+                const uint32_t g0 = chirp_addr<D0>(s, 2u * c, k);
+                v.x = s.in[g0];
+                if (FORMB) v.x += ca * s.ga[g0] + cb * s.gb[g0];
+                if (two) {
+                    const uint32_t g1 = chirp_addr<D0>(s, 2u * c + 1u, k);
+                    v.y = s.in[g1];
+                    if (FORMB) v.y += ca * s.ga[g1] + cb * s.gb[g1];
+                }
+            } else {
+                // V[k] = conj(q[k]) (X[k] - i X[m-k]), X[m] = 0; Z = V_a + i V_b; the DFT below takes conj Z
+                const uint32_t kp = n ? m - n : 0u;
+                double2 Xk, Xm = make_double2(0.0, 0.0);
+                Xk.x = s.in[chirp_addr<D0>(s, 2u * c, n)];
+                Xk.y = two ? s.in[chirp_addr<D0>(s, 2u * c + 1u, n)] : 0.0;
+                if (n) {
+                    Xm.x = s.in[chirp_addr<D0>(s, 2u * c, kp)];
+                    Xm.y = two ? s.in[chirp_addr<D0>(s, 2u * c + 1u, kp)] : 0.0;
+                }
+                const double2 qc = cconj(s.qw[n]);
+                const double2 va = cmul(qc, make_double2(Xk.x, -Xm.x));
+                const double2 vb = cmul(qc, make_double2(Xk.y, -Xm.y));
+                v = make_double2(va.x - vb.y, -(va.y + vb.x));
+            }
+            v = cmul(v, s.chirp[n]);
+        }
+        buf[(cl * C + cc) * LP + s.reva[n1]] = v;
+    }
+    __syncthreads();
+    mr_fft<false, false>(buf, s.twa, int(ncl * C), int(a), LP, s.pa);
+    for (uint32_t e = threadIdx.x; e < nel; e += dctg::NT) {
+        uint32_t cl, cc, k1, col = 0;
+        chirp_el<false>(s, e, ncl, cl, cc, k1);
+        const uint32_t c = c0 + cl;
+        if (!chirp_col(s, t0, cc, col) || c >= s.nclt) continue;
+        s.scr[(size_t(c) * a + k1) * b + col] = cmul(buf[(cl * C + cc) * LP + k1], dd_tw(s.t1, s.t2, col * k1));
+    }
+}
+
+// rows of the scratch, all lines' alike (no global side): u = c a + k1
+__global__ __launch_bounds__(dctg::NT) void k_chr(const ChirpArgs s) {
+    if (s.skip && *s.skip) return;
+    if (s.ctl && s.ctl->done) return;
+    extern __shared__ double2 buf[];   // G lines of b + PAD complex slots
+    const uint32_t a = s.a, b = s.b, G = s.G;
+    const int LP = int(b) + spec::PAD;
+    const size_t u0 = size_t(blockIdx.x) * G, nU = size_t(s.nclt) * a;
+    const uint32_t nel = G * b;
+    for (uint32_t e = threadIdx.x; e < nel; e += dctg::NT) {
+        const uint32_t g = s.fb.div(e), n2 = e - g * b;
+        buf[g * LP + s.revb[n2]] = u0 + g < nU ? s.scr[(u0 + g) * b + n2] : make_double2(0.0, 0.0);
+    }
+    __syncthreads();
+    mr_fft<false, false>(buf, s.twb, int(G), int(b), LP, s.pb);
+    for (uint32_t e = threadIdx.x; e < nel; e += dctg::NT) {
+        const uint32_t g = s.fb.div(e), k2 = e - g * b;
+        if (u0 + g >= nU) continue;
+        const uint32_t u = uint32_t(u0 + g), k1 = u - s.fa.div(u) * a;
+        buf[g * LP + k2] = cmul(buf[g * LP + k2], s.H[k1 * b + k2]);
+    }
+    __syncthreads();
+    mr_fft<true, true>(buf, s.twb, int(G), int(b), LP, s.pb);
+    for (uint32_t e = threadIdx.x; e < nel; e += dctg::NT) {
+        const uint32_t g = s.fb.div(e), n2 = e - g * b;
+        if (u0 + g >= nU) continue;
+        const uint32_t u = uint32_t(u0 + g), k1 = u - s.fa.div(u) * a;
+        s.scr[(u0 + g) * b + n2] = cmul(buf[g * LP + s.revb[n2]], cconj(dd_tw(s.t1, s.t2, n2 * k1)));
+    }
+}
+
+template <bool INV, bool D0>
+__global__ __launch_bounds__(dctg::NT) void k_cho(const ChirpArgs s) {
+    if (s.skip && *s.skip) return;
+    if (s.ctl && s.ctl->done) return;
+    extern __shared__ double2 buf[];   // (tq / 2) * 2 Ch lines of a + PAD complex slots
+    const uint32_t a = s.a, b = s.b, m = s.m, C = 2u * s.Ch, ncl = uint32_t(s.tq) >> 1;
+    const int LP = int(a) + spec::PAD;
+    const uint32_t lt = s.fnct.div(blockIdx.x), ct = blockIdx.x - lt * s.nct;
+    const uint32_t c0 = lt * ncl, t0 = ct * s.Ch;
+    const uint32_t nel = ncl * C * a;
+
+    for (uint32_t e = threadIdx.x; e < nel; e += dctg::NT) {
+        uint32_t cl, cc, k1, col = 0;
+        chirp_el<false>(s, e, ncl, cl, cc, k1);
+        const uint32_t c = c0 + cl;
+        double2 v = make_double2(0.0, 0.0);
+        if (chirp_col(s, t0, cc, col) && c < s.nclt) v = s.scr[(size_t(c) * a + k1) * b + col];
+        buf[(cl * C + cc) * LP + k1] = v;
+    }
+    __syncthreads();
+    mr_fft<true, true>(buf, s.twa, int(ncl * C), int(a), LP, s.pa);   // sample n1 at reva[n1]
+    for (uint32_t e = threadIdx.x; e < nel; e += dctg::NT) {
+        uint32_t cl, cc, n1, col = 0;
+        chirp_el<!D0>(s, e, ncl, cl, cc, n1);
+        const uint32_t c = c0 + cl;
+        if (!chirp_col(s, t0, cc, col) || c >= s.nclt) continue;
+        const uint32_t n = n1 * b + col;
+        if (n >= m) continue;
+        const bool two = 2u * c + 1u < s.nlines;
+        const double2 Z1 = cmul(buf[(cl * C + cc) * LP + s.reva[n1]], s.chirp[n]);
+        if (INV) {   // the real lines, conj of the DFT of conj V, back in the Makhoul order
+            const uint32_t k = 2u * n < m ? 2u * n : 2u * (m - 1u - n) + 1u;
+            s.out[chirp_addr<D0>(s, 2u * c, k)] = Z1.x;
+            if (two) s.out[chirp_addr<D0>(s, 2u * c + 1u, k)] = -Z1.y;
+            continue;
+        }
+        // Z[m - k]: column (m - n2) mod b, the partner slot of this orbit (the slot itself at a fixed point), row
+        // (m - k) / b; k = 0 pairs with itself
+        double2 Z2 = Z1;
+        if (n) {
+            const uint32_t kp = m - n, n1p = s.fb.div(kp), colp = kp - n1p * b;
+            const uint32_t ccp = colp == col ? cc : (cc >= s.Ch ? cc - s.Ch : cc + s.Ch);
+            Z2 = cmul(buf[(cl * C + ccp) * LP + s.reva[n1p]], s.chirp[kp]);
+        }
+        const double2 q1 = s.qw[n];
+        const double2 Ap = make_double2(0.5 * (Z1.x + Z2.x), 0.5 * (Z1.y - Z2.y));
+        const double2 Bp = make_double2(0.5 * (Z1.y + Z2.y), -0.5 * (Z1.x - Z2.x));
+        s.out[chirp_addr<D0>(s, 2u * c, n)] = q1.x * Ap.x - q1.y * Ap.y;
+        if (two) s.out[chirp_addr<D0>(s, 2u * c + 1u, n)] = q1.x * Bp.x - q1.y * Bp.y;
+    }
+}
+
+// the library's convolution length for m: the smallest 2-3-5-7-smooth M >= 2m - 1 with a factorisation a b, both
+// <= kSplitMax; a the largest such divisor <= sqrt(M). false: none (m > (4096^2 + 1) / 2)
+bool dct_chirp_auto(uint32_t m, uint32_t* a, uint32_t* b) {
+    const uint64_t lim = uint64_t(kSplitMax) * kSplitMax;
+    for (uint64_t M = std::max<uint64_t>(4, 2 * uint64_t(m) - 1); M <= lim; ++M) {
+        uint64_t r = M;
+        for (uint64_t q : {2, 3, 5, 7})
+            while (r % q == 0) r /= q;
+        if (r != 1) continue;
+        uint64_t best = 0;
+        for (uint64_t d = 2; d * d <= M; ++d)
+            if (M % d == 0 && M / d <= kSplitMax) best = d;
+        if (best) {
+            *a = uint32_t(best);
+            *b = uint32_t(M / best);
+            return true;
+        }
+    }
+    return false;
+}
+
+// the three launches of a chirp pass (both directions: k_chc, k_chr, k_cho). A timed pass (g_timed) spans them: the
+// start event on the first, the stop event on the last.
+static hipError_t launch_dct_chirp(const SpecPlan& sp, const Geom& g, hipStream_t st, int mode, int d, const double* in,
+                                   const double* ga, double ca, const double* gb, double cb, double* out,
+                                   const AdmmCtl* ctl, const int32_t* skip) {
+    const DctChirp& dc = sp.chirp[d];
+    const uint32_t m = g.m[d], a = dc.a, b = dc.b;
+    if (mode == SPEC_MID || d >= g.p - 1 || a < 2 || b < 2 || uint64_t(a) * b + 1 < 2 * uint64_t(m) ||
+        a > kSplitMax || b > kSplitMax || !sp.stw || !sp.srev || !sp.sscr)
+        return hipErrorInvalidValue;
+    ChirpArgs s{};
+    s.in = in;
+    s.ga = ga;
+    s.gb = gb;
+    s.ca = ca;
+    s.cb = cb;
+    s.out = out;
+    s.scr = reinterpret_cast<double2*>(sp.sscr);
+    s.twa = reinterpret_cast<const double2*>(sp.stw + dc.twa);
+    s.twb = reinterpret_cast<const double2*>(sp.stw + dc.twb);
+    s.t1 = reinterpret_cast<const double2*>(sp.stw + dc.t1);
+    s.t2 = reinterpret_cast<const double2*>(sp.stw + dc.t2);
+    s.chirp = reinterpret_cast<const double2*>(sp.stw + dc.chirp);
+    s.qw = reinterpret_cast<const double2*>(sp.stw + dc.qw);
+    s.H = reinterpret_cast<const double2*>(sp.stw + dc.H);
+    s.reva = sp.srev + dc.reva;
+    s.revb = sp.srev + dc.revb;
+    s.m = m;
+    s.a = a;
+    s.b = b;
+    s.stride = g.stride[d];
+    s.nlines = g.N / m;
+    s.nclt = (s.nlines + 1u) / 2u;
+    if (2 * size_t(s.nclt) * a * b > sp.sscr_cap) return hipErrorInvalidValue;
+    s.skip = skip;
+    s.ctl = ctl;
+    if (!sub_fft_plan(a, &s.pa) || !sub_fft_plan(b, &s.pb)) return hipErrorInvalidValue;
+    const bool d0 = d == 0, formb = ga != nullptr, inv = mode == SPEC_INV;
+    if (formb && (inv || !gb)) return hipErrorInvalidValue;
+    s.r = m % b;
+    s.nlo = s.r / 2u + 1u;
+    s.norb = s.nlo + (s.r + b) / 2u - s.r;
+    // columns: one line pair (d = 0) or <= 8 adjacent ones (128-B rows) by as many orbits (two columns each) as the
+    // LDS holds, in even tiles; one orbit of a = 4096 is 131 KB
+    const uint32_t slots = uint32_t(dsp::SLOTS);
+    uint32_t tq = d0 ? 2u : 16u;
+    while (tq > 2u && (tq / 2u) * 2u * (a + 1u) > slots) tq /= 2u;
+    const uint32_t hmax = std::min(s.norb, std::max(1u, slots / ((tq / 2u) * 2u * (a + 1u))));
+    s.tq = int(tq);
+    s.nct = (s.norb + hmax - 1u) / hmax;
+    s.Ch = (s.norb + s.nct - 1u) / s.nct;
+    s.G = std::min<uint32_t>(2u * uint32_t(dsp::GMAX), std::max(1u, slots / (b + 1u)));
+    s.fds = FastDiv(s.stride);
+    s.fC = FastDiv(2u * s.Ch);
+    s.fa = FastDiv(a);
+    s.fb = FastDiv(b);
+    s.fnct = FastDiv(s.nct);
+    const uint64_t gc = uint64_t((s.nclt + tq / 2u - 1u) / (tq / 2u)) * s.nct;
+    const uint64_t gr = (uint64_t(s.nclt) * a + s.G - 1u) / s.G;
+    if (gc > 0x7fffffffull || gr > 0x7fffffffull || uint64_t(s.nclt) * a > 0xffffffffull)
+        return hipErrorInvalidValue;
+    const dim3 gridc{uint32_t(gc)}, gridr{uint32_t(gr)}, block(dctg::NT);
+    const size_t smc = size_t(tq / 2u) * 2u * s.Ch * (a + 1u) * sizeof(double2), smr = size_t(s.G) * (b + 1u) * sizeof(double2);
+    const TimedLaunch tl = g_timed;
+    g_timed = TimedLaunch{};
+    auto go = [&](auto kern, dim3 grid, size_t smem, int which) {
+        if (smem > 65536)
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      int(smem));
+        if (g_launch_log.on) launch_log_push(reinterpret_cast<const void*>(kern), grid, block);
+        hipEvent_t e0 = which == 0 ? tl.start : nullptr, e1 = which == 2 ? tl.stop : nullptr;
+        if (e0 || e1) hipExtLaunchKernelGGL(kern, grid, block, uint32_t(smem), st, e0, e1, 0u, s);
+        else hipLaunchKernelGGL(kern, grid, block, uint32_t(smem), st, s);
+    };
+    if (!inv) {
+        if (d0) {
+            if (formb) go(k_chc<false, true, true>, gridc, smc, 0);
+            else go(k_chc<false, true, false>, gridc, smc, 0);
+        } else {
+            if (formb) go(k_chc<false, false, true>, gridc, smc, 0);
+            else go(k_chc<false, false, false>, gridc, smc, 0);
+        }
+        go(k_chr, gridr, smr, 1);
+        if (d0) go(k_cho<false, true>, gridc, smc, 2);
+        else go(k_cho<false, false>, gridc, smc, 2);
+    } else {
+        if (d0) go(k_chc<true, true, false>, gridc, smc, 0);
+        else go(k_chc<true, false, false>, gridc, smc, 0);
+        go(k_chr, gridr, smr, 1);
+        if (d0) go(k_cho<true, true>, gridc, smc, 2);
+        else go(k_cho<true, false>, gridc, smc, 2);
+    }
+    return hipGetLastError();
+}
+
 bool dct_pcg_fusable(const Geom& g, size_t partial_words) {
     const uint32_t m = g.m[0];
     if (g.p < 2 || m < 64 || m > 4096 || (m & (m - 1)) != 0 || probe_env("MVTV_DCT_LDS") || probe_env("MVTV_PCGS_NINE"))
@@ -5468,6 +5822,11 @@ hipError_t launch_dct_pass(const SpecPlan& sp, const Geom& g, hipStream_t s, int
     if (d < g.p - 1 && sp.split[d].a > 0) {
         if (fold || (pf && pf->mode)) return hipErrorInvalidValue;
         return launch_dct_split(sp, g, s, mode, d, in, ga, ca, gb, cb, out, ctl, skip);
+    }
+    // a leading dimension by Bluestein's identity over a two-pass convolution (mvtv_problem_dct_chirp): any m
+    if (d < g.p - 1 && sp.chirp[d].a > 0) {
+        if (fold || (pf && pf->mode)) return hipErrorInvalidValue;
+        return launch_dct_chirp(sp, g, s, mode, d, in, ga, ca, gb, cb, out, ctl, skip);
     }
     if (m > 4096) return hipErrorInvalidValue;
     if (a.fold && (!formb || !gb || !ctl || (1u << a.L) != m || (1u << a.ls) != a.stride || a.L < 3 ||
