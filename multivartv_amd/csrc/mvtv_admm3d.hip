@@ -266,9 +266,6 @@ bool edge4d_ok(const Geom& g);
 hipError_t launch_edge4d(const Geom& g, int order, int umode, hipStream_t s, const double* theta, double* edges,
                          double t_old, double c_old, double t_new, const double* theta_old, double* partials,
                          int* nparts, const AdmmCtl* ctl);
-hipError_t launch_gather4d(const Geom& g, int order, int umode, hipStream_t s, const double* edges, double t,
-                           double* g_alpha, double* g_u, const double* g_uprev, double c_prev, double* partials,
-                           int* nparts, const AdmmCtl* ctl);
 bool gather4_ok(const Geom& g);
 hipError_t launch_gather4(const Geom& g, int order, int umode, hipStream_t s, const double* edges, double t,
                           double* g_alpha, double* g_u, const double* g_uprev, double c_prev, double* partials,
@@ -330,11 +327,9 @@ hipError_t launch_gather3d(const Geom& g, int order, int umode, hipStream_t s, c
         if (scratch4 && gather4_ok(g))
             return launch_gather4(g, order, umode, s, edges, t, g_alpha, g_u, g_uprev, c_prev, partials, nparts, ctl,
                                   scratch4, fold);
-        // 4-D: the marching gather (k_gather4d) reads ~65 neighbour words per cell through L1/L2 and
-        // measured slower at 128^4 (20.8 vs 18.4 ms) than the grid-stride kernel; opt-in only
-        static const bool marching = probe_env("MVTV_G4D") != nullptr;
-        if (marching)
-            return launch_gather4d(g, order, umode, s, edges, t, g_alpha, g_u, g_uprev, c_prev, partials, nparts, ctl);
+        // 4-D without the two-pass gather's scratch: the grid-stride kernel (a one-pass marching gather read ~65
+        // neighbour words per cell through L1/L2 and measured slower at 128^4, 20.8 vs 18.4 ms; it was removed and
+        // last existed in commit ae72d5c)
         const int grid = int(std::min<uint64_t>((uint64_t(g.N) + kThreads - 1) / kThreads, kMaxGrid));
         *nparts = grid;
         return launch_gather(g, order, umode, Launch{s, grid}, edges, t, g_alpha, g_u, g_uprev, c_prev, partials, ctl);
@@ -947,97 +942,6 @@ __global__ __launch_bounds__(e4d::NT) void k_edge4d(const Edge4dArgs a) {
     block_reduce_store<ER_N, 1, e4d::NT>(red, a.partials);
 }
 
-template <int ORD, int UM, bool PREV, int NB>
-__global__ __launch_bounds__(e4d::NT) void k_gather4d(const Edge4dArgs a) {
-    constexpr int P = 4, PC = 8;
-    const Geom& g = a.g;
-    double tt = a.t, c_prev = a.c_prev;
-    if (a.ctl) {
-        if (a.ctl->done) return;
-        tt = a.ctl->t_next;
-        c_prev = a.ctl->c_prev;
-    }
-    double red[GR_N] = {0.0, 0.0, 0.0};
-    const Tile4 T = tile4(a);
-    if (T.valid && T.x < int(g.m[0]) && T.y < int(g.m[1])) {
-        const uint32_t m0 = g.m[0], m01 = g.m[0] * g.m[1], pl = m01 * g.m[2];
-        const bool okx = T.x > 0, oky = T.y > 0, okz = T.z > 0;
-        const uint32_t base = uint32_t(T.z) * m01 + uint32_t(T.y) * m0 + uint32_t(T.x);
-        uint32_t qoff[PC];
-        bool qok[PC];
-#pragma unroll
-        for (int q = 0; q < PC; ++q) {
-            const bool bx = q & 1, by = (q >> 1) & 1, bz = (q >> 2) & 1;
-            qok[q] = (!bx || okx) && (!by || oky) && (!bz || okz);
-            qoff[q] = qok[q] ? (bx ? 1u : 0u) + (by ? m0 : 0u) + (bz ? m01 : 0u) : 0u;
-        }
-        double qa_prev[NB], qu_prev[NB];
-#pragma unroll
-        for (int k = 0; k < NB; ++k) qa_prev[k] = qu_prev[k] = 0.0;
-        auto plane_q = [&](auto kc, int w, double& qa, double& qu) {
-            constexpr int k = decltype(kc)::value;
-            constexpr int S = sprime_mask(block_code(k, P, ORD), P);
-            constexpr int SI = S & 7;
-            const uint32_t ib = uint32_t(w) * pl + base;
-            qa = 0.0;
-            qu = 0.0;
-#pragma unroll
-            for (int q = 0; q < PC; ++q) {
-                if ((q & ~SI) != 0) continue;
-                const double vv = a.edges[eix(g, k, ib - qoff[q])];
-                const double v = qok[q] ? vv : 0.0;
-                const bool neg = __builtin_popcount(q) & 1;
-                if constexpr (UM == U_FROM_Z) {
-                    const double cl = clampd(v, tt);
-                    const double al = v - cl;
-                    qa = neg ? qa - al : qa + al;
-                    qu = neg ? qu + cl : qu - cl;
-                } else {
-                    qu = neg ? qu - v : qu + v;
-                }
-            }
-        };
-        if (T.w0 > 0) {
-            static_for<0, NB>([&](auto kc) {
-                constexpr int k = decltype(kc)::value;
-                constexpr int S = sprime_mask(block_code(k, P, ORD), P);
-                if constexpr ((S & 8) != 0) plane_q(kc, T.w0 - 1, qa_prev[k], qu_prev[k]);
-            });
-        }
-        for (int w = T.w0; w < T.w1; ++w) {
-            double ga = 0.0, gu = 0.0;
-            static_for<0, NB>([&](auto kc) {
-                constexpr int k = decltype(kc)::value;
-                constexpr int S = sprime_mask(block_code(k, P, ORD), P);
-                double qa, qu;
-                plane_q(kc, w, qa, qu);
-                double ca = qa, cu = qu;
-                if constexpr ((S & 8) != 0) {
-                    ca -= qa_prev[k];
-                    cu -= qu_prev[k];
-                    qa_prev[k] = qa;
-                    qu_prev[k] = qu;
-                }
-                ga = fma(g.w[k], ca, ga);
-                gu = fma(g.w[k], cu, gu);
-            });
-            const uint32_t i = uint32_t(w) * pl + base;
-            if constexpr (UM == U_FROM_Z) __builtin_nontemporal_store(ga, a.g_alpha + i);
-            __builtin_nontemporal_store(gu, a.g_u + i);
-            red[GR_GU2] = fma(gu, gu, red[GR_GU2]);
-            if constexpr (PREV) {
-                const double gp = c_prev * __builtin_nontemporal_load(a.g_uprev + i);
-                const double db = gu - gp, da = ga + gp;
-                red[GR_S2B] = fma(db, db, red[GR_S2B]);
-                red[GR_S2A] = fma(da, da, red[GR_S2A]);
-            }
-        }
-    }
-    if (!T.valid)
-        for (int k = 0; k < GR_N; ++k) red[k] = 0.0;
-    block_reduce_store<GR_N, 0, e4d::NT>(red, a.partials);
-}
-
 namespace {
 Edge4dArgs e4d_args(const Geom& g) {
     Edge4dArgs a{};
@@ -1094,37 +998,6 @@ hipError_t launch_edge4d(const Geom& g, int order, int umode, hipStream_t s, con
     }
     if (umode == U_EXPLICIT) return dth ? go(k_edge4d<1, U_EXPLICIT, true, 15>) : go(k_edge4d<1, U_EXPLICIT, false, 15>);
     return dth ? go(k_edge4d<1, U_FROM_Z, true, 15>) : go(k_edge4d<1, U_FROM_Z, false, 15>);
-}
-
-hipError_t launch_gather4d(const Geom& g, int order, int umode, hipStream_t s, const double* edges, double t,
-                           double* g_alpha, double* g_u, const double* g_uprev, double c_prev, double* partials,
-                           int* nparts, const AdmmCtl* ctl) {
-    Edge4dArgs a = e4d_args(g);
-    a.edges = const_cast<double*>(edges);   // read only in k_gather4d
-    a.g_alpha = g_alpha;
-    a.g_u = g_u;
-    a.g_uprev = g_uprev;
-    a.partials = partials;
-    a.t = t;
-    a.c_prev = c_prev;
-    a.ctl = ctl;
-    const int grid = (a.nblocks + 7) / 8 * 8;
-    *nparts = grid;
-    const bool prev = g_uprev != nullptr;
-    auto go = [&](auto kern) {
-        klaunch(kern, dim3(grid), dim3(e4d::NT), 0, s, a);
-        return hipGetLastError();
-    };
-    if (order == 0) {
-        if (umode == U_EXPLICIT) return prev ? go(k_gather4d<0, U_EXPLICIT, true, 15>) : go(k_gather4d<0, U_EXPLICIT, false, 15>);
-        return prev ? go(k_gather4d<0, U_FROM_Z, true, 15>) : go(k_gather4d<0, U_FROM_Z, false, 15>);
-    }
-    if (g.nb == 14) {
-        if (umode == U_EXPLICIT) return prev ? go(k_gather4d<1, U_EXPLICIT, true, 14>) : go(k_gather4d<1, U_EXPLICIT, false, 14>);
-        return prev ? go(k_gather4d<1, U_FROM_Z, true, 14>) : go(k_gather4d<1, U_FROM_Z, false, 14>);
-    }
-    if (umode == U_EXPLICIT) return prev ? go(k_gather4d<1, U_EXPLICIT, true, 15>) : go(k_gather4d<1, U_EXPLICIT, false, 15>);
-    return prev ? go(k_gather4d<1, U_FROM_Z, true, 15>) : go(k_gather4d<1, U_FROM_Z, false, 15>);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1311,7 +1184,7 @@ __global__ __launch_bounds__(g4::NTB) void k_gather4b(const Gather4Args a) {
 }
 
 bool gather4_ok(const Geom& g) {
-    if (g.p != 4 || probe_env("MVTV_G4D") || probe_env("MVTV_G4_OFF")) return false;
+    if (g.p != 4 || probe_env("MVTV_G4_OFF")) return false;
     const uint32_t pl = g.m[0] * g.m[1] * g.m[2];
     const int nwp = int(g.iend / pl) - int(g.ibeg / pl);
     const int per = int((pl + g4::NTB - 1) / g4::NTB);

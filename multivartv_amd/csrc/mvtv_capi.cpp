@@ -422,7 +422,7 @@ void bluestein_tables(uint32_t m, uint32_t M, std::vector<double>& out) {
             out.push_back(double((*v)[k].real() / (long double)M));
             out.push_back(double((*v)[k].imag() / (long double)M));
         }
-    for (uint32_t k = 0; k < M; ++k) {   // (k_dctb reads k < M/2, k_dctb8's radix-8 stages k < M)
+    for (uint32_t k = 0; k < M; ++k) {   // (k_dctb8's radix-8 stages read k < M)
         const long double ang = -2.0L * pi * (long double)k / (long double)M;
         out.push_back(double(cosl(ang)));
         out.push_back(double(sinl(ang)));
@@ -479,7 +479,7 @@ mvtv_status spectral_plan(mvtv_problem* P) {
             perm.push_back(pos);
         }
     }
-    // Bluestein tables of the lengths without a 2-3-5-7 plan (k_dctb; mvtv_spectral.hip)
+    // Bluestein tables of the lengths without a 2-3-5-7 plan (k_dctb8; mvtv_spectral.hip)
     std::vector<double> blu;
     for (int j = 0; j < P->g.p; ++j) {
         const uint32_t m = (P->slab && j == P->g.p - 1) ? uint32_t(P->m_global) : P->g.m[j];
@@ -773,7 +773,7 @@ bool split_on(const mvtv_problem* P) {
 }
 
 // Which meshes the spectral solve takes. Cosine transforms of any length <= 4096: FFT plans for 2-3-5-7 lengths,
-// Bluestein (k_dctb) for the rest; a longer leading dimension with a factorisation a * b, both 2-3-5-7-smooth and
+// Bluestein (k_dctb8) for the rest; a longer leading dimension with a factorisation a * b, both 2-3-5-7-smooth and
 // <= 4096, in two passes, and any leading dimension under mvtv_problem_dct_chirp (dct_split_setup). The last dimension
 // is never transformed: on one GPU it may have any length (spec_long: the blocked line solve); a slab rank keeps the
 // old rule for every dimension (its loop has the substructured solve over the ranks)
@@ -869,53 +869,24 @@ mvtv_status line_sweeps(mvtv_problem* P, double* x, double sigma, double w0, con
 mvtv_status spectral_solve(mvtv_problem* P, double sigma, const double* oty, const double* ga, double ca,
                            const double* gb, double cb, double* x, const AdmmCtl* ctl = nullptr, double w0 = 1.0,
                            const int32_t* skip = nullptr, bool fold = false) {
-    // pass order: forward along dims order[0..p-2], forward/divide/inverse along order[p-1], inverse
-    // back; the MID dimension defaults to p-1 (MVTV_DCT_MID selects another one for experiments)
     const int p = P->g.p;
-    static const int mid_env = [] {
-        const char* e = probe_env("MVTV_DCT_MID");
-        return e ? std::atoi(e) : -1;
-    }();
-    const int mid = (mid_env >= 1 && mid_env < p) ? mid_env : p - 1;
-    // 3-D: dim 2 forward (b formed on load), the two marching passes (dim-0 transforms + the dim-1 line solves),
-    // dim 2 inverse: 9N words instead of 11N
-    if (!P->slab && march_ok(P->g) && !split_on(P)) {
-        int h = P->tstart(ga ? (fold ? MVTV_K_DCT_FOLD : MVTV_K_DCT_FIRST) : MVTV_K_DCT);
+    // the first pass of a solve, along dim 0 (p = 1: the only one, mode 2): oty into x, b formed on load when ga is
+    // given (fold: b = oty + fold_ka s + fold_kb g_u, g_u read after a rho change)
+    auto first_pass = [&](int mode) -> hipError_t {
         if (ga && fold)
-            HIP_TRY(launch_dct_pass(P->spec, P->g, P->stream, 0, 2, oty, ga, 1.0, gb, 0.0, x, sigma, w0, ctl, 0, 0.0, skip,
-                                    nullptr, true));
-        else if (ga)
-            HIP_TRY(launch_dct_pass(P->spec, P->g, P->stream, 0, 2, oty, ga, ca, gb ? gb : ga, gb ? cb : 0.0, x, sigma, w0,
-                                    ctl, 0, 0.0, skip));
-        else
-            HIP_TRY(launch_dct_pass(P->spec, P->g, P->stream, 0, 2, oty, nullptr, 0.0, nullptr, 0.0, x, sigma, w0, ctl, 0,
-                                    0.0, skip));
-        P->tstop(h);
-        h = P->tstart(MVTV_K_DCT);
-        HIP_TRY(launch_march(P->spec, P->g, P->stream, false, x, sigma, w0, ctl, skip));
-        P->tstop(h);
-        h = P->tstart(MVTV_K_DCT);
-        HIP_TRY(launch_march(P->spec, P->g, P->stream, true, x, sigma, w0, ctl, skip));
-        P->tstop(h);
-        h = P->tstart(MVTV_K_DCT);
-        HIP_TRY(launch_dct_pass(P->spec, P->g, P->stream, 1, 2, x, nullptr, 0.0, nullptr, 0.0, x, sigma, w0, ctl, 0, 0.0,
-                                skip));
-        P->tstop(h);
-        return MVTV_OK;
-    }
+            return launch_dct_pass(P->spec, P->g, P->stream, mode, 0, oty, ga, 1.0, gb, 0.0, x, sigma, w0, ctl, 0, 0.0,
+                                   skip, nullptr, true);
+        if (ga)
+            return launch_dct_pass(P->spec, P->g, P->stream, mode, 0, oty, ga, ca, gb ? gb : ga, gb ? cb : 0.0, x, sigma,
+                                   w0, ctl, 0, 0.0, skip);
+        return launch_dct_pass(P->spec, P->g, P->stream, mode, 0, oty, nullptr, 0.0, nullptr, 0.0, x, sigma, w0, ctl, 0,
+                               0.0, skip);
+    };
     // 3-D, m1 = 512: dim-0 forward (b formed on load), the down sweep, the chunk interface, the up sweep, dim-0
     // inverse: 9N words and the chunks' carries instead of 11N (line_sweep_setup chose ls_chunks)
-    if (!P->slab && sweeps_on(P) && mid == p - 1) {
+    if (!P->slab && sweeps_on(P)) {
         int h = P->tstart(ga ? (fold ? MVTV_K_DCT_FOLD : MVTV_K_DCT_FIRST) : MVTV_K_DCT);
-        if (ga && fold)
-            HIP_TRY(launch_dct_pass(P->spec, P->g, P->stream, 0, 0, oty, ga, 1.0, gb, 0.0, x, sigma, w0, ctl, 0, 0.0, skip,
-                                    nullptr, true));
-        else if (ga)
-            HIP_TRY(launch_dct_pass(P->spec, P->g, P->stream, 0, 0, oty, ga, ca, gb ? gb : ga, gb ? cb : 0.0, x, sigma, w0,
-                                    ctl, 0, 0.0, skip));
-        else
-            HIP_TRY(launch_dct_pass(P->spec, P->g, P->stream, 0, 0, oty, nullptr, 0.0, nullptr, 0.0, x, sigma, w0, ctl, 0,
-                                    0.0, skip));
+        HIP_TRY(first_pass(0));
         P->tstop(h);
         MVTV_TRY(line_sweeps(P, x, sigma, w0, ctl, skip));
         h = P->tstart(MVTV_K_DCT);
@@ -924,16 +895,8 @@ mvtv_status spectral_solve(mvtv_problem* P, double sigma, const double* oty, con
         P->tstop(h);
         return MVTV_OK;
     }
-    // probe builds: MVTV_DCT_REV=1 takes the other dims in descending order (the first pass, b formed on load, and the
-    // last inverse pass then run along dim p - 2 instead of the contiguous dim 0)
-    static const bool rev = probe_env("MVTV_DCT_REV") != nullptr;
-    int order[MVTV_MAX_DIMS], n = 0;
-    for (int d = 0; d < p; ++d)
-        if (d != mid) order[n++] = d;
-    if (rev) std::reverse(order, order + n);
-    order[n++] = mid;
     // m0 = m1 <= 128: dims 0 and 1 in one pass each way (k_plane8: the plane stays on chip between them)
-    const bool plane = !rev && mid >= 2 && plane_pass_ok(P->g) && !split_on(P);
+    const bool plane = plane_pass_ok(P->g) && !split_on(P);
     if (plane) {
         const int h = P->tstart(ga ? (fold ? MVTV_K_DCT_FOLD : MVTV_K_DCT_FIRST) : MVTV_K_DCT);
         if (ga && fold)
@@ -944,26 +907,20 @@ mvtv_status spectral_solve(mvtv_problem* P, double sigma, const double* oty, con
             HIP_TRY(launch_plane_pass(P->spec, P->g, P->stream, 0, oty, nullptr, 0.0, nullptr, 0.0, x, ctl, skip));
         P->tstop(h);
     }
-    for (int t = plane ? 2 : 0; t < p; ++t) {
-        const int d = order[t];
-        const bool first = t == 0;
-        const int mode = t == p - 1 ? 2 : 0;
-        const int h = P->tstart(first ? (fold ? MVTV_K_DCT_FOLD : MVTV_K_DCT_FIRST) : MVTV_K_DCT);
-        if (first && ga && fold)   // b = oty + fold_ka s + fold_kb g_u formed on load (g_u read after a rho change)
-            HIP_TRY(launch_dct_pass(P->spec, P->g, P->stream, mode, d, oty, ga, 1.0, gb, 0.0, x, sigma, w0, ctl, 0, 0.0,
-                                    skip, nullptr, true));
-        else if (first && ga)   // b = oty + ca*ga + cb*gb formed on load
-            HIP_TRY(launch_dct_pass(P->spec, P->g, P->stream, mode, d, oty, ga, ca, gb ? gb : ga, gb ? cb : 0.0, x,
-                                    sigma, w0, ctl, 0, 0.0, skip));
+    for (int d = plane ? 2 : 0; d < p; ++d) {
+        const int mode = d == p - 1 ? 2 : 0;
+        const int h = P->tstart(d == 0 ? (fold ? MVTV_K_DCT_FOLD : MVTV_K_DCT_FIRST) : MVTV_K_DCT);
+        if (d == 0)
+            HIP_TRY(first_pass(mode));
         else
-            HIP_TRY(launch_dct_pass(P->spec, P->g, P->stream, mode, d, first ? oty : x, nullptr, 0.0, nullptr, 0.0, x,
-                                    sigma, w0, ctl, 0, 0.0, skip));
+            HIP_TRY(launch_dct_pass(P->spec, P->g, P->stream, mode, d, x, nullptr, 0.0, nullptr, 0.0, x, sigma, w0, ctl, 0,
+                                    0.0, skip));
         P->tstop(h);
     }
-    for (int t = p - 2; t >= (plane ? 2 : 0); --t) {
+    for (int d = p - 2; d >= (plane ? 2 : 0); --d) {
         const int h = P->tstart(MVTV_K_DCT);
-        HIP_TRY(launch_dct_pass(P->spec, P->g, P->stream, 1, order[t], x, nullptr, 0.0, nullptr, 0.0, x, sigma, w0,
-                                ctl, 0, 0.0, skip));
+        HIP_TRY(launch_dct_pass(P->spec, P->g, P->stream, 1, d, x, nullptr, 0.0, nullptr, 0.0, x, sigma, w0, ctl, 0, 0.0,
+                                skip));
         P->tstop(h);
     }
     if (plane) {
@@ -1659,16 +1616,13 @@ mvtv_status mvtv_admm_run(mvtv_problem* P, const mvtv_admm_opts* opts_in, double
         // FOLD (variant B): the fused 3-D kernel stores s = rho (D^T alpha + D^T u) in P->ga instead of D^T alpha, so
         // the next solve's first pass reads oty and s (2N words) instead of oty, D^T alpha and D^T u (3N); after a
         // control step that changed rho it forms oty + (rho'/rho) s + rho' (c - 1) D^T u (AdmmCtl::fold_ka / _kb)
-        // (the first pass transforms dim 0, or dim 2 on k_march meshes)
-        const bool marching = !P->slab && march_ok(P->g) && !split_on(P);
-        const uint32_t m0 = marching ? P->g.m[2] : P->g.m[0];
+        // (the first pass transforms dim 0)
+        const uint32_t m0 = P->g.m[0];
         const bool fold_path = fused ? (P->g.p == 2 || P->g.p == 3)
                                      : (P->g.p == 4 && P->e3d && P->g4 != nullptr && gather4_ok(P->g));   // two-pass 4-D
-        // on k_march meshes the folded first pass runs along dim 2 at stride m0 * m1, which must be a power of two too
-        const uint64_t fold_stride = marching ? uint64_t(P->g.m[0]) * P->g.m[1] : 1;
         const bool fold = fold_path && variant == MVTV_VARIANT_RCPP && m0 >= 8 && m0 <= 4096 &&
-                          (m0 & (m0 - 1)) == 0 && (fold_stride & (fold_stride - 1)) == 0 && !split_on(P) &&
-                          !probe_env("MVTV_FOLD_OFF") && !probe_env("MVTV_DCT_LDS") && !probe_env("MVTV_DCT_MID");
+                          (m0 & (m0 - 1)) == 0 && !split_on(P) && !probe_env("MVTV_FOLD_OFF") &&
+                          !probe_env("MVTV_DCT_LDS");
         auto enqueue = [&](int j) -> mvtv_status {
             double* gp = gbuf[j & 1];
             double* gn = gbuf[(j + 1) & 1];

@@ -356,7 +356,7 @@ struct SpecPlan {
     double* lam = nullptr;    // per dim: m_j eigenvalues 4 sin^2(pi k/(2 m_j)) of the Neumann Laplacian
     uint32_t* perm = nullptr; // per dim (at perm_off): position of sample k in the mixed-radix FFT's input order
     uint32_t tw_off[kMaxDims] = {0, 0, 0, 0}, twq_off[kMaxDims] = {0, 0, 0, 0}, lam_off[kMaxDims] = {0, 0, 0, 0};
-    // lengths without a 2-3-5-7 plan (Bluestein, k_dctb): per such dim, at blu_off (doubles), m complex chirp values
+    // lengths without a 2-3-5-7 plan (Bluestein, k_dctb8): per such dim, at blu_off (doubles), m complex chirp values
     // e^{-i pi n^2/m}, then M values each of the forward and inverse kernels' transforms / M, then M twiddles
     // e^{-2 pi i k/M}; blu_M[j] = M = 2^ceil(log2(2 m_j - 1)), 0 for a planned dim
     double* blu = nullptr;
@@ -384,13 +384,6 @@ bool plane_pass_ok(const Geom& g);
 hipError_t launch_plane_pass(const SpecPlan& sp, const Geom& g, hipStream_t s, int mode, const double* in,
                              const double* ga, double ca, const double* gb, double cb, double* out,
                              const AdmmCtl* ctl = nullptr, const int32_t* skip = nullptr, bool fold = false);
-// 3-D meshes solved as dim-2 forward pass, k_march forward, k_march backward, dim-2 inverse pass (m0 a power of two in
-// [256, 2048], m1 a multiple of the march step, 128 <= m2 <= 4096)
-bool march_ok(const Geom& g);
-// the marching passes over every dim-2 frequency plane of x, in place: forward (dim-0 DCT of the rows + Thomas
-// forward elimination along dim 1) or backward (back substitution + inverse dim-0 DCT, scaled by m1 / N)
-hipError_t launch_march(const SpecPlan& sp, const Geom& g, hipStream_t s, bool bwd, double* x, double sigma, double w0,
-                        const AdmmCtl* ctl = nullptr, const int32_t* skip = nullptr);
 // The dim-1 transforms and the dim-2 line solve of a 3-D mesh as two marching sweeps with the chunk interface between
 // them (k_sweep, k_trisr_iface): dim-0 forward pass, down sweep, interface, up sweep, dim-0 inverse pass. Shapes:
 // p = 3, m1 = 512, m0 a multiple of 16. line_sweep_chunks: the cost model's chunk count over dim 2 (<= m2,
@@ -410,7 +403,8 @@ bool dct_pcg_fusable(const Geom& g, size_t partial_words);
 // radices (8, 4, 2, 3, 5, 7 in stage order) of a line length m = 2^a 3^b 5^c 7^d; false for any other m
 bool dct_radix_plan(uint32_t m, int* rad, int* nrad);
 // mode 0 forward DCT-II, 1 inverse (DCT-III, unnormalised), 2 forward + divide by mu * N + inverse;
-// ga != nullptr forms the input as in + ca*ga + cb*gb. In place (in == out) is allowed. m_d <= 4096, except mode 2
+// ga != nullptr forms the input as in + ca*ga + cb*gb (d = 0 only: the first pass of a solve; hipErrorInvalidValue
+// along another dimension). In place (in == out) is allowed. m_d <= 4096, except mode 2
 // along d = p - 1 while sp.lb.nblk > 0: the blocked line solve (three launches; p = 1: 16-B aligned arrays), and modes
 // 0 / 1 along a dimension with sp.split[d].a > 0: the two-pass transform (two launches through sp.sscr; its
 // frequencies stay in the order position b k1 + k2 <-> k = k1 + a k2, the order of that dimension's lam table), and
@@ -420,23 +414,21 @@ hipError_t launch_dct_pass(const SpecPlan& sp, const Geom& g, hipStream_t s, int
                            const double* ga, double ca, const double* gb, double cb, double* out, double sigma,
                            double w0, const AdmmCtl* ctl = nullptr, uint32_t q_off = 0, double inv_n = 0.0,
                            const int32_t* skip = nullptr, const PcgFuse* pf = nullptr, bool fold = false);
-// Slab-decomposed last-dimension solve by substructuring (mvtv_spectral.hip, k_tris): og = the owned planes
-// (m[p-1] = their count, stride[p-1] = plane lines). phase 1: per line the first / last rows of G, H, K of
-// the local block into coef [chunk s][6][line in chunk]; phase 3: x = scale * (local solve with the
-// neighbours' values lr [chunk s][2][line in chunk]) in place. lo_ext / hi_ext: the lines continue on the
+// Slab-decomposed last-dimension solve by substructuring (mvtv_spectral.hip, k_trisr): og = the owned planes
+// (m[p-1] = their count, stride[p-1] = plane lines). phase 1: per line the local block's kTriSlabNcoef numbers
+// (its F at its last row, B at its first) into coef [chunk s][2][line in chunk]; phase 3: x = scale * (local solve
+// with the block's 2 carries lr [chunk s][2][line in chunk]) in place. lo_ext / hi_ext: the lines continue on the
 // rank below / above. launch_tri_iface: the interface systems of one chunk's lines over the G ranks.
 // sigma, w0: the operator c0 = w0 + ..., c1 (ignored when ctl gives sigma); skip: return at once when *skip
 hipError_t launch_tri_slab(const SpecPlan& sp, const Geom& og, hipStream_t s, int phase, double* x, double* coef,
                            const double* lr, uint32_t chunk, int lo_ext, int hi_ext, double scale,
                            const AdmmCtl* ctl, double sigma = 1.0, double w0 = 1.0, const int32_t* skip = nullptr);
-// a block of n planes splits into k_tris segments (<= 64 of <= 32 rows): false for e.g. a prime n > 64
+// a block of n planes splits into k_trisr segments (<= 64 of <= 32 rows): false for e.g. a prime n > 64
 bool tri_slab_ok(uint32_t n);
-// The factorised form (k_trisr, the default; round 6): phase 1 writes 2 numbers per line [chunk s][2][line in chunk]
-// (the block's F at its last row, B at its first), the interface gives every block its 2 carries, phase 3 reads them
-// from lr; the Thomas form (k_tris, probe builds with MVTV_TRI_IIR=0) exchanges 6 and 2. tri_slab_ncoef(): the phase-1
-// numbers per line (the first all-to-all's count). launch_tri_iface: og = the owned planes' geometry (its dims
-// 0..p-2 and the line constants), rank = the chunk's owner, mg = the global plane count.
-int tri_slab_ncoef();
+// the phase-1 numbers per line (the first all-to-all's count; the Thomas form of rounds 4 and 5 sent 6)
+constexpr int kTriSlabNcoef = 2;
+// launch_tri_iface: og = the owned planes' geometry (its dims 0..p-2 and the line constants), rank = the chunk's owner,
+// mg = the global plane count.
 hipError_t launch_tri_iface(const SpecPlan& sp, const Geom& og, hipStream_t s, double* coef_in, double* lr_out,
                             uint32_t chunk, int G, int rank, uint32_t mg, const AdmmCtl* ctl, double sigma = 1.0,
                             double w0 = 1.0, const int32_t* skip = nullptr);

@@ -85,7 +85,7 @@ struct mvtv_problem {
     // mvtv_problem_dct_chirp: the convolution's factors (a, b) per dimension; a = -1 the library's, 0 off
     int32_t chirp_forced[kMaxDims][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};
     bool spec_long = false;       // ... with a last dimension longer than 4096 (the blocked line solve, spec.lb)
-    bool spec_pow2 = false;       // ... and a power of two (k_dct8 / k_tri passes)
+    bool spec_pow2 = false;       // ... and a power of two (k_dct8 / k_trir passes)
     bool spec_lead = false;       // dims 0..p-2 have a transform (the slab loop: the last dimension may have any length)
     bool e3d = false;             // z-marching 3-D edge kernels
     bool f3d = false;             // fused 3-D edge update + gather (needs the second edge buffer)

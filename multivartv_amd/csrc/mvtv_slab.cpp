@@ -5,7 +5,7 @@
 // Rank r owns planes [zb, ze) of the last dimension plus one ghost plane below / above
 // (mvtv_problem_create_slab). Per iteration:
 //   theta-solve  cosine transforms along dims 0..p-2 on the owned planes, in place; the tridiagonal line
-//                solves along dim p-1 by substructuring (mvtv_spectral.hip k_tris): each rank reduces its
+//                solves along dim p-1 by substructuring (mvtv_spectral.hip k_trisr): each rank reduces its
 //                block of every line to 6 numbers, an all-to-all brings each chunk of lines' numbers to
 //                one rank, which solves the lines' interface systems over the ranks and sends every rank
 //                its lines' 2 neighbour values back; each rank then solves its blocks; inverse transforms
@@ -836,7 +836,7 @@ mvtv_status slab_run(mvtv_problem* P, mvtv_comm* C, const mvtv_admm_opts* opts, 
     {   // every rank must enqueue the same loop: the fused pass or not, the same edge layout (the z halo moves
         // whole planes in it), W or not. One sum of the flags, with the ranks' shares of sum W and sum W^2; a
         // mismatch fails on every rank alike
-        // slot 7: this rank's block of every line can be cut into the line solves' segments (k_tris: <= 64
+        // slot 7: this rank's block of every line can be cut into the line solves' segments (k_trisr: <= 64
         // segments of <= 32 rows); checked here, before any rank enters a collective the infeasible one would skip
         const bool lines_ok = G == 1 || tri_slab_ok(sg.nz);
         double flags[9] = {P->f3d ? 1.0 : 0.0, P->g.eaos ? 1.0 : 0.0, P->e3d ? 1.0 : 0.0, double(sg.plane),
@@ -942,8 +942,10 @@ mvtv_status slab_run(mvtv_problem* P, mvtv_comm* C, const mvtv_admm_opts* opts, 
     og.iend = og.N;
     double* th = P->theta + sg.off;
     const size_t ln = sg.lines, ch = sg.chunk;
-    double* co_send = P->slab_iface;          // [chunk s][6][line in chunk]
-    double* co_recv = co_send + 6 * ln;       // [rank r][6][line in my chunk]
+    // (co_send / co_recv keep the 6 ln doubles each of the allocation's layout; the factorised solve uses the first
+    // kTriSlabNcoef ln)
+    double* co_send = P->slab_iface;          // [chunk s][kTriSlabNcoef][line in chunk]
+    double* co_recv = co_send + 6 * ln;       // [rank r][kTriSlabNcoef][line in my chunk]
     double* lr_send = co_recv + 6 * ln;       // [rank r][2][line in my chunk]
     double* lr_recv = lr_send + 2 * ln;       // [chunk s][2][line in chunk]
     const double scale = 1.0 / double(sg.lines);   // the forward transforms along dims 0..p-2 (unnormalised)
@@ -1077,7 +1079,7 @@ mvtv_status slab_run(mvtv_problem* P, mvtv_comm* C, const mvtv_admm_opts* opts, 
         } else {
             HIP_TRY(launch_tri_slab(P->spec, og, s, 1, z, co_send, nullptr, uint32_t(ch), rk > 0, rk < G - 1, scale,
                                     nullptr, sigma, w0, skip));
-            MVTV_TRY(crit_a2a(co_send, co_recv, size_t(tri_slab_ncoef()), EV_CO, EV_COD));
+            MVTV_TRY(crit_a2a(co_send, co_recv, size_t(kTriSlabNcoef), EV_CO, EV_COD));
             HIP_TRY(launch_tri_iface(P->spec, og, s, co_recv, lr_send, uint32_t(ch), G, rk, sg.mg, nullptr, sigma, w0,
                                      skip));
             MVTV_TRY(crit_a2a(lr_send, lr_recv, 2, EV_LR, EV_LRD));
@@ -1196,7 +1198,7 @@ mvtv_status slab_run(mvtv_problem* P, mvtv_comm* C, const mvtv_admm_opts* opts, 
                 HIP_TRY(launch_tri_slab(P->spec, og, s, 1, th, co_send, nullptr, uint32_t(ch), rk > 0, rk < G - 1, scale,
                                         P->ctl));
                 P->tstop(h);
-                MVTV_TRY(crit_a2a(co_send, co_recv, size_t(tri_slab_ncoef()), EV_CO, EV_COD));
+                MVTV_TRY(crit_a2a(co_send, co_recv, size_t(kTriSlabNcoef), EV_CO, EV_COD));
                 HIP_TRY(launch_tri_iface(P->spec, og, s, co_recv, lr_send, uint32_t(ch), G, rk, sg.mg, P->ctl));
                 MVTV_TRY(crit_a2a(lr_send, lr_recv, 2, EV_LR, EV_LRD));
                 h = P->tstart(MVTV_K_DCT);

@@ -77,11 +77,11 @@ struct SpecArgs {
     FastDiv fper[8], fL[8];   // stage s: butterflies per line (m / rad[s]) and the span before it
     const uint32_t* perm;     // position of sample k in the digit-reversed Makhoul order (this dim)
     int32_t xcd;              // k_dct8: tiles dealt to the XCDs in contiguous runs (grid a multiple of 8)
-    int32_t xrun;             // k_dctg / k_dctm / k_dctb / k_dctb8 / k_trig: the same for any grid (xcd_run)
+    int32_t xrun;             // k_dctg / k_dctm / k_dctb8 / k_trigr: the same for any grid (xcd_run)
     PcgFuse pf;               // k_dct8 PC = 1 / 2: the PCG vector work of the preconditioner's d = 0 passes
     int32_t fold;             // FORMB from the folded s (k_dct8, ctl): b = in + fold_ka ga [+ fold_kb gb if ctl->fix]
     int32_t pair16;           // k_dct8 d = 0 forward / inverse: coefficients through LDS as 16-B pairs (dct_pair16)
-    // Bluestein lengths (k_dctb; L = log2 M then, tw = the length-M FFT twiddles): the chirp c[n] = e^{-i pi n^2/m}
+    // Bluestein lengths (k_dctb8; L = log2 M then, tw = the length-M FFT twiddles): the chirp c[n] = e^{-i pi n^2/m}
     // and the transforms / M of the forward / inverse convolution kernels
     const double2* bchirp;
     const double2* bvf;
@@ -533,6 +533,7 @@ __global__ __launch_bounds__((spec8::ShapeK<L, TQW>::NT)) void k_dct8(const Spec
     using S = spec8::ShapeK<L, TQW>;
     static_assert(PC == 0 || (D0 && !FORMB && (PC == 1 ? MODE == SPEC_FWD : MODE == SPEC_INV)),
                   "PCG fusion: d = 0 forward (PC 1) / inverse (PC 2) passes only");
+    static_assert(D0 || !FORMB, "b is formed on load along dim 0 only");
     // scalars into locals: writing into the by-value argument struct would demote it to scratch
     double sigma = a.sigma, ca = a.ca, cb = a.cb;
     if (a.skip && *a.skip) return;
@@ -1092,261 +1093,6 @@ __global__ __launch_bounds__((1 << L) / 2 * (1 << L) / 8) void k_plane8(const Sp
 }
 
 // =============================================================================================
-// 3-D meshes: the dim-0 transforms and the tridiagonal solve along dim 1 in two marching passes.
-//
-// Transforms along different dimensions commute, so a 3-D solve can run the dim-2 forward transform first (b formed
-// on load) and leave dims 0 and 1 for last: after the dim-0 and dim-2 transforms, line (k0, k2) along dim 1 carries
-// c0 I + c1 T (k_tri's operator). A workgroup owns one dim-2 frequency plane (m0 x m1, contiguous) and marches
-// its rows (dim-1 positions), NR at a time:
-//   forward  (k_march<L, false>): DCT-II of the NR rows along dim 0 (k_dct8's register radix-8 stages), then one
-//            Thomas forward-elimination step per row for every k0 line, x'_i = (g_i - A x'_{i-1}) / den_i, the
-//            previous row's x' carried in registers; x' written in place;
-//   backward (k_march<L, true>): rows in reverse, x_i = x'_i - (A / den_i) x_{i+1}, then the inverse DCT along
-//            dim 0 of the NR rows; theta written in place (scaled by inv_n m1).
-// The dim-1 forward / inverse transform passes and the separate tridiagonal pass become these two: a 3-D solve
-// moves 9N words instead of 11N (the first pass 3N, then 2N each).
-//
-// The backward sweep needs den_i in reverse order, which the forward recurrence den_i = B - A^2 / den_{i-1}
-// cannot give without storing it. Its closed form does: den_i = p_{i+1} / p_i with p_{i+1} = B p_i - A^2 p_{i-1},
-// p_0 = 1, p_1 = B0 = c0 + c1 (the Neumann first row), so with the roots l1 > l2 of l^2 - B l + A^2 and
-// q = l2 / l1, r = beta / alpha:
-//     den_i = l1 (1 + r q^{i+1}) / (1 + r q^i),  l1 = (B + s) / 2,  s = sqrt(c0 (c0 + 4 c1)),
-//     r = 4 c0 c1 / (c0 + s)^2,  q = 4 c1^2 / (B + s)^2,  1 - q = (c0 + s)(B + s + 2 c1) / (B + s)^2
-//     (B = c0 + 2 c1, A = -c1)
-// every term free of cancellation (a numpy study against long-double Thomas: as accurate as fp64 Thomas for
-// c1 / c0 from 1e-2 to 1e7). The last row subtracts c1 (Neumann end). Both sweeps evaluate the same closed form,
-// so they apply one factorisation; q^i comes from one exp per line per step, then q-multiplications over the
-// step's rows.
-namespace march {
-template <int L>
-struct Shape {
-    static constexpr int M = 1 << L;
-    static constexpr int TPL = M / 8;          // FFT threads per complex line (k_dct8's D0 mapping)
-    static constexpr int NCL = 2048 / M;       // complex lines = row pairs per step
-    static constexpr int NR = 2 * NCL;         // rows per step
-    static constexpr int NT = NCL * TPL;       // 256 threads
-    static constexpr int LPT = M / NT;         // k0 lines per thread in the elimination
-};
-}  // namespace march
-
-template <int L, bool BWD>
-__global__ __launch_bounds__(256) void k_march(const SpecArgs a, uint32_t m1) {
-    using S = spec8::Shape<L>;
-    using T = march::Shape<L>;
-    constexpr int M = T::M, TPL = T::TPL, NCL = T::NCL, NR = T::NR, NT = T::NT, LPT = T::LPT, R0 = S::R0;
-    static_assert(NT == 256 && LPT >= 1, "k_march: 256 threads, m0 in [256, 2048]");
-    double sigma = a.sigma;
-    if (a.skip && *a.skip) return;
-    if (a.ctl) {
-        if (a.ctl->done) return;
-        sigma = a.ctl->sigma;
-    }
-    __shared__ double2 buf[NCL * S::LP];   // FFT exchange (k_dct8's slot layout)
-    __shared__ double C[NR * M];          // the step's coefficients [row][k0]
-    const uint32_t e = blockIdx.x;        // dim-2 frequency
-    const uint32_t pb = e * (uint32_t(M) * m1);
-    const int t = threadIdx.x;
-    const int j = t % TPL, c = t / TPL;
-    double2* const X = buf + c * S::LP;
-    const int cx = c & 7;
-    const double2* __restrict__ tw = a.tw;
-    const double2* __restrict__ twq = a.twq;
-
-    // line constants of k0 = t + l NT: c0 + c1 T along dim 1 (dims 0 and 2 transformed), then the closed form
-    double A[LPT], il1[LPT], rr[LPT], qq[LPT], lq[LPT], c1v[LPT];
-    {
-        const double lam2 = a.lam[a.lam_off[2] + e];
-#pragma unroll
-        for (int l = 0; l < LPT; ++l) {
-            const double lam0 = a.lam[a.lam_off[0] + uint32_t(t + l * NT)];
-            double c0 = a.w0, c1 = 0.0;
-            for (int Sm = 1; Sm < 8; ++Sm) {
-                if (a.cS[Sm] == 0.0) continue;
-                double prod = sigma * a.cS[Sm];
-                if (Sm & 1) prod *= lam0;
-                if (Sm & 4) prod *= lam2;
-                if (Sm & 2) c1 += prod;
-                else c0 += prod;
-            }
-            const double B = c0 + 2.0 * c1, sq = sqrt(c0 * (c0 + 4.0 * c1));
-            const double l1 = 0.5 * (B + sq);
-            const double cs = c0 + sq, bs = B + sq;
-            A[l] = -c1;
-            c1v[l] = c1;
-            il1[l] = 1.0 / l1;
-            rr[l] = 4.0 * c0 * c1 / (cs * cs);
-            // log q: from q = 4 c1^2 / (B + s)^2 while q is small (-inf when c1 = 0), from 1 - q near 1 (where the
-            // rounding of 1 - q ~ 1 could also push log1p's argument below -1)
-            const double qd = 4.0 * c1 * c1 / (bs * bs);
-            lq[l] = qd < 0.5 ? log(qd) : log1p(-(cs * (bs + 2.0 * c1)) / (bs * bs));
-            qq[l] = qd < 0.5 ? qd : exp(lq[l]);
-        }
-    }
-    // q^i at the first row of a step (exact start: no drift over the march)
-    auto qpow = [&](int l, uint32_t i) -> double { return i == 0 ? 1.0 : exp(double(i) * lq[l]); };
-
-    // the natural-order spectrum in X -> DCT-II coefficients (k, M - k) for k = j + s TPL (k_plane8's fwd_coeff)
-    auto fwd_coeff = [&](int k, double2& Xk, double2& Xmk) {
-        const int ka = k, kb = k ? M - k : M / 2;
-        const double2 Z1 = X[spec8::slot(ka, cx)], Z2 = X[spec8::slot(kb, cx)];
-        const double2 q1 = twq[ka], q2 = twq[kb];
-        if (k == 0) {
-            Xk = make_double2(q1.x * Z1.x, q1.x * Z1.y);
-            Xmk = make_double2(q2.x * Z2.x, q2.x * Z2.y);
-        } else {
-            const double2 Ap = make_double2(0.5 * (Z1.x + Z2.x), 0.5 * (Z1.y - Z2.y));
-            const double2 Bp = make_double2(0.5 * (Z1.y + Z2.y), -0.5 * (Z1.x - Z2.x));
-            Xk = make_double2(q1.x * Ap.x - q1.y * Ap.y, q1.x * Bp.x - q1.y * Bp.y);
-            Xmk = make_double2(q2.x * Ap.x + q2.y * Ap.y, q2.x * Bp.x + q2.y * Bp.y);
-        }
-    };
-    // coefficients (k, M - k) -> the IFFT input of the Makhoul sequence, in X (k_plane8's inv_spectrum)
-    auto inv_spectrum = [&](int k, double2 Xk, double2 Xmk) {
-        const int ka = k, kb = k ? M - k : M / 2;
-        const double2 q1 = cconj(twq[ka]), q2 = cconj(twq[kb]);
-        if (k == 0) {
-            const double2 va2 = cmul(q2, make_double2(Xmk.x, -Xmk.x));
-            const double2 vb2 = cmul(q2, make_double2(Xmk.y, -Xmk.y));
-            X[spec8::slot(0, cx)] = Xk;
-            X[spec8::slot(M / 2, cx)] = make_double2(va2.x - vb2.y, va2.y + vb2.x);
-        } else {
-            const double2 va1 = cmul(q1, make_double2(Xk.x, -Xmk.x));
-            const double2 vb1 = cmul(q1, make_double2(Xk.y, -Xmk.y));
-            const double2 va2 = cmul(q2, make_double2(Xmk.x, -Xk.x));
-            const double2 vb2 = cmul(q2, make_double2(Xmk.y, -Xk.y));
-            X[spec8::slot(ka, cx)] = make_double2(va1.x - vb1.y, va1.y + vb1.x);
-            X[spec8::slot(kb, cx)] = make_double2(va2.x - vb2.y, va2.y + vb2.x);
-        }
-    };
-
-    double2 z[8];
-    if constexpr (!BWD) {
-        double xs[LPT];   // x'_{i-1} per line
-#pragma unroll
-        for (int l = 0; l < LPT; ++l) xs[l] = 0.0;
-        double2 lv[8];    // the step's rows (2c, 2c + 1) at (2n, 2n + 1), n = j + s4 TPL
-        auto issue = [&](uint32_t i0) {
-#pragma unroll
-            for (int s4 = 0; s4 < 4; ++s4)
-#pragma unroll
-                for (int r = 0; r < 2; ++r)
-                    lv[2 * s4 + r] = ldnt2(a.in + pb + (i0 + uint32_t(2 * c + r)) * uint32_t(M) +
-                                           uint32_t(2 * (j + s4 * TPL)));
-        };
-        issue(0);
-        for (uint32_t i0 = 0; i0 < m1; i0 += NR) {
-#pragma unroll
-            for (int s4 = 0; s4 < 4; ++s4) {
-                const int n = j + s4 * TPL;
-                X[spec8::slot(n, cx)] = make_double2(lv[2 * s4].x, lv[2 * s4 + 1].x);
-                X[spec8::slot(M - 1 - n, cx)] = make_double2(lv[2 * s4].y, lv[2 * s4 + 1].y);
-            }
-            if (i0 + NR < m1) issue(i0 + NR);   // in flight during this step (LDS-only barriers below)
-            lds_barrier();
-#pragma unroll
-            for (int i = 0; i < 8; ++i) z[i] = X[spec8::slot(stage_in_pos<L, R0>(j, i), cx)];
-            stages_from<L, R0, 1, false, false, true>(z, j, X, cx, tw);   // natural-order spectrum in X
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                const int k = j + s * TPL, kb = k ? M - k : M / 2;
-                double2 Xk, Xmk;
-                fwd_coeff(k, Xk, Xmk);
-                C[(2 * c) * M + k] = Xk.x;
-                C[(2 * c + 1) * M + k] = Xk.y;
-                C[(2 * c) * M + kb] = Xmk.x;
-                C[(2 * c + 1) * M + kb] = Xmk.y;
-            }
-            lds_barrier();
-            // forward elimination along dim 1, rows i0 .. i0 + NR - 1
-#pragma unroll
-            for (int l = 0; l < LPT; ++l) {
-                const uint32_t k0 = uint32_t(t + l * NT);
-                double qi = qpow(l, i0);
-                double u = 1.0 + rr[l] * qi;
-#pragma unroll
-                for (int r = 0; r < NR; ++r) {
-                    const uint32_t i = i0 + uint32_t(r);
-                    qi *= qq[l];
-                    const double u1 = 1.0 + rr[l] * qi;
-                    // 1 / den_i = u_i / (l1 u_{i+1}); the last row: den - c1
-                    const double w = (i + 1 == m1) ? 1.0 / (u1 / (u * il1[l]) - c1v[l]) : u * il1[l] / u1;
-                    xs[l] = (C[r * M + int(k0)] - A[l] * xs[l]) * w;
-                    __builtin_nontemporal_store(xs[l], a.out + pb + i * uint32_t(M) + k0);
-                    u = u1;
-                }
-            }
-            // (the next step's first LDS writes touch X, whose reads ended before the barrier above; its C
-            // writes come after its first barrier)
-        }
-    } else {
-        const double sc = a.inv_n * double(m1);   // the dim-0 and dim-2 transforms are unnormalised
-        double xn[LPT];   // x_{i+1} per line
-#pragma unroll
-        for (int l = 0; l < LPT; ++l) xn[l] = 0.0;
-        double lx[LPT][NR];   // the step's x' rows at this thread's lines
-        auto issue = [&](uint32_t i0) {
-#pragma unroll
-            for (int l = 0; l < LPT; ++l)
-#pragma unroll
-                for (int r = 0; r < NR; ++r)
-                    lx[l][r] = __builtin_nontemporal_load(a.in + pb + (i0 + uint32_t(r)) * uint32_t(M) + uint32_t(t + l * NT));
-        };
-        issue(m1 - NR);
-        for (int i0 = int(m1) - NR; i0 >= 0; i0 -= NR) {
-            double cur[LPT][NR];
-#pragma unroll
-            for (int l = 0; l < LPT; ++l)
-#pragma unroll
-                for (int r = 0; r < NR; ++r) cur[l][r] = lx[l][r];
-            if (i0 >= NR) issue(uint32_t(i0 - NR));
-            // back substitution, rows i0 + NR - 1 down to i0
-#pragma unroll
-            for (int l = 0; l < LPT; ++l) {
-                const uint32_t k0 = uint32_t(t + l * NT);
-                double u[NR + 1];
-                double qi = qpow(l, uint32_t(i0));
-                u[0] = 1.0 + rr[l] * qi;
-#pragma unroll
-                for (int r = 1; r <= NR; ++r) {
-                    qi *= qq[l];
-                    u[r] = 1.0 + rr[l] * qi;
-                }
-#pragma unroll
-                for (int r = NR - 1; r >= 0; --r) {
-                    const uint32_t i = uint32_t(i0 + r);
-                    double x = cur[l][r];
-                    if (i + 1 < m1) x -= A[l] * u[r] * il1[l] / u[r + 1] * xn[l];   // e_i = A / den_i
-                    xn[l] = x;
-                    C[r * M + int(k0)] = x * sc;
-                }
-            }
-            lds_barrier();
-            // inverse DCT along dim 0 of rows (2c, 2c + 1)
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                const int k = j + s * TPL, kb = k ? M - k : M / 2;
-                inv_spectrum(k, make_double2(C[(2 * c) * M + k], C[(2 * c + 1) * M + k]),
-                             make_double2(C[(2 * c) * M + kb], C[(2 * c + 1) * M + kb]));
-            }
-            lds_barrier();
-#pragma unroll
-            for (int i = 0; i < 8; ++i) z[i] = X[spec8::slot(stage_in_pos<L, R0>(j, i), cx)];
-            stages_from<L, R0, 1, true, false, true>(z, j, X, cx, tw);   // output through X
-#pragma unroll
-            for (int s4 = 0; s4 < 4; ++s4) {
-                const int n = j + s4 * TPL;
-                const double2 v0 = X[spec8::slot(n, cx)], v1 = X[spec8::slot(M - 1 - n, cx)];
-                stnt2(a.out + pb + uint32_t(i0 + 2 * c) * uint32_t(M) + uint32_t(2 * n), make_double2(v0.x, v1.x));
-                stnt2(a.out + pb + uint32_t(i0 + 2 * c + 1) * uint32_t(M) + uint32_t(2 * n), make_double2(v0.y, v1.y));
-            }
-            // (the next step writes C before its first barrier: every C read of this step came before this step's
-            // second barrier; its X writes come after its first barrier, which every thread reaches only after its
-            // stores above)
-        }
-    }
-}
-
-// =============================================================================================
 // Mixed-radix lengths: m = 2^a 3^b 5^c 7^d <= 4096 that is not a power of two (meshes such as
 // 24 x 40, 100^3 or 1000^2). Same Makhoul pairing and pass structure as k_dct8, with the complex
 // FFT of length m run in LDS as in-place Cooley-Tukey stages of radix 8, 4, 2, 3, 5, 7: decimation
@@ -1461,6 +1207,7 @@ __device__ __forceinline__ void mr_fft(double2* buf, const double2* tw, int ncl,
 
 template <int MODE, bool D0, bool FORMB>
 __global__ __launch_bounds__(dctg::NT) __attribute__((amdgpu_waves_per_eu(4))) void k_dctg(const SpecArgs a) {
+    static_assert(D0 || !FORMB, "b is formed on load along dim 0 only");
     double sigma = a.sigma, ca = a.ca, cb = a.cb;
     if (a.skip && *a.skip) return;
     if (a.ctl) {
@@ -1613,7 +1360,7 @@ __global__ __launch_bounds__(dctg::NT) __attribute__((amdgpu_waves_per_eu(4))) v
 // 1000 = 2 4 5^3): k_dct8's Stockham scheme with a compile-time radix plan. A thread holds V complex values
 // of one complex line (two real lines, Makhoul pairing) and runs its V / R radix-R butterflies of each stage in
 // registers; LDS carries the exchanges between stages (k_dctg: one in-place LDS stage per radix with FastDiv
-// index math and a permutation-table load per element). FWD and INV passes (the last dimension takes k_trig or
+// index math and a permutation-table load per element). FWD and INV passes (the last dimension takes k_trigr or
 // k_dctg's MID pass); TQ = 16 real lines per workgroup, lanes over the lines for a strided pass (16-B accesses
 // of a line pair, 128-B rows when the tile does not straddle a stride boundary), over j for d = 0.
 namespace dctm {
@@ -1689,13 +1436,14 @@ __device__ __forceinline__ int dctm_in_pos(int j, int i) {
     return j + (i / R) * T + (i % R) * (M / R);
 }
 
-// NCLW complex lines (2 NCLW real lines) per workgroup: 8 (128-B rows) or 4 (64-B rows, half the LDS: more workgroups
-// a CU)
+// NCLW complex lines (2 NCLW real lines) per workgroup: 4 (64-B rows; half the LDS of the 8-line tile that round 5
+// measured against it: more workgroups a CU) or 1 (few lines)
 template <int M, int MODE, bool D0, bool FORMB, int NCLW = dctm::NCL>
 __global__ __launch_bounds__(NCLW * dctm::Shape<M>::T) void k_dctm(const SpecArgs a) {
     using S = dctm::Shape<M>;
     constexpr int T = S::T, NCL = NCLW, V = S::V, TQ = 2 * NCLW;
     static_assert(MODE == SPEC_FWD || MODE == SPEC_INV, "FWD / INV passes");
+    static_assert(D0 || !FORMB, "b is formed on load along dim 0 only");
     double ca = a.ca, cb = a.cb;
     bool rd_gb = true;
     if (a.skip && *a.skip) return;
@@ -1897,16 +1645,10 @@ static bool launch_dctm(SpecArgs& a, hipStream_t s, int mode, bool d0, bool form
     if (!d0 && (a.stride & 1u)) return false;   // line pairs must be adjacent words
     // 8-line tiles (500: 32 KB of LDS, up to five workgroups a CU against two with 16 lines; 1000: two against one):
     // 500^3 137.5 / 138.3 -> 141.6 / 142.4 ADMM it/s on one box, the first pass 0.93 -> 0.86 ms
-    // (profiles/r05/v11_dctm_ncl4); few lines (1000 x 1000: 125 such tiles) one line pair per workgroup. Probe builds:
-    // MVTV_DCTM_NCL=8 / 4 / 1 forces the tile
-    static const int ncl_env = [] {
-        const char* e = probe_env("MVTV_DCTM_NCL");
-        return e ? std::atoi(e) : 0;
-    }();
+    // (profiles/r05/v11_dctm_ncl4); few lines (1000 x 1000: 125 such tiles) one line pair per workgroup
     static const bool few_off = probe_flag("MVTV_FEW_LINES_OFF");
-    const int ncl = (ncl_env == 8 || ncl_env == 4 || ncl_env == 1)
-                        ? ncl_env
-                        : (few_off ? 4 : few_lines_tq(a.nlines, 8, 2) / 2);
+    const int ncl = few_off ? 4 : few_lines_tq(a.nlines, 8, 2) / 2;
+    // (b is formed on load along dim 0 only: launch_dct_pass)
 #define MVTV_DCTM(MM, NC)                                                                                       \
     do {                                                                                                        \
         const dim3 grid((a.nlines + uint32_t(2 * NC) - 1) / uint32_t(2 * NC));                                 \
@@ -1918,17 +1660,14 @@ static bool launch_dctm(SpecArgs& a, hipStream_t s, int mode, bool d0, bool form
             if (formb) klaunch(k_dctm<MM, SPEC_FWD, true, true, NC>, grid, block, 0, s, a);                     \
             else klaunch(k_dctm<MM, SPEC_FWD, true, false, NC>, grid, block, 0, s, a);                          \
         } else {                                                                                                \
-            if (formb) klaunch(k_dctm<MM, SPEC_FWD, false, true, NC>, grid, block, 0, s, a);                    \
-            else klaunch(k_dctm<MM, SPEC_FWD, false, false, NC>, grid, block, 0, s, a);                         \
+            klaunch(k_dctm<MM, SPEC_FWD, false, false, NC>, grid, block, 0, s, a);                              \
         }                                                                                                       \
     } while (0)
     if (m == 500) {
-        if (ncl == 8) MVTV_DCTM(500, 8);
-        else if (ncl == 4) MVTV_DCTM(500, 4);
+        if (ncl == 4) MVTV_DCTM(500, 4);
         else MVTV_DCTM(500, 1);
     } else {
-        if (ncl == 8) MVTV_DCTM(1000, 8);
-        else if (ncl == 4) MVTV_DCTM(1000, 4);
+        if (ncl == 4) MVTV_DCTM(1000, 4);
         else MVTV_DCTM(1000, 1);
     }
 #undef MVTV_DCTM
@@ -1950,8 +1689,6 @@ static void launch_dctg(SpecArgs& a, hipStream_t s, int mode, bool d0, bool form
         if (d0) {
             if (formb) MVTV_DCTG(SPEC_FWD, true, true);
             else MVTV_DCTG(SPEC_FWD, true, false);
-        } else if (formb) {
-            MVTV_DCTG(SPEC_FWD, false, true);
         } else {
             MVTV_DCTG(SPEC_FWD, false, false);
         }
@@ -1989,227 +1726,21 @@ bool dct_radix_plan(uint32_t m, int* rad, int* nrad) {
 //
 //   Y[k] = c[k] sum_n (y[n] c[n]) b[k - n],   c[n] = e^{s i pi n^2 / m},  b[j] = conj c[j]   (s = -1 / +1)
 //
-// a linear convolution, evaluated as a circular one of length M = 2^ceil(log2(2m - 1)) with k_dct's radix-2^2
-// LDS FFT (fft_lines): the chirped input goes in at bit-reversed slots, the forward FFT leaves natural order,
-// the product with the transform of b (a per-dimension table, 1/M folded in) goes through the inverse FFT,
-// which leaves the convolution at bit-reversed slots again. So every length-m quantity lives at slot
-// brev_M(n): the Makhoul pairing (k, m - k), the MID divide and b formed on load are k_dctg's, read and
-// written there. Per line pair: two length-M FFTs per transform (four in a MID pass); fp64 round-off grows
-// as log M, like the planned FFTs'.
-namespace dctb {
-constexpr int NT = 256;   // spec::NT: fft_lines strides over the workgroup's threads
-}
-
-template <int MODE, bool D0, bool FORMB>
-__global__ __launch_bounds__(dctb::NT) void k_dctb(const SpecArgs a) {
-    double sigma = a.sigma, ca = a.ca, cb = a.cb;
-    if (a.skip && *a.skip) return;
-    if (a.ctl) {
-        if (a.ctl->done) return;
-        sigma = a.ctl->sigma;
-        ca = a.ctl->rho;
-        cb = a.ctl->rho * a.ctl->c_prev;
-    }
-    extern __shared__ double2 buf[];   // tq / 2 complex lines of M + PAD slots (launch-time size)
-    __shared__ double lc0[16], lc1[16];
-    const int m = int(a.m[a.d]);
-    const int L = a.L, M = 1 << L;     // a.L = log2 M here
-    const int tq = a.tq, ncl = tq >> 1, lncl = __ffs(ncl) - 1;
-    const int LP = M + spec::PAD;
-    const uint32_t q0 = (a.xrun ? xcd_run(blockIdx.x, gridDim.x) : blockIdx.x) * uint32_t(tq);
-    const double2* __restrict__ chirp = a.bchirp;   // c[n] = e^{-i pi n^2 / m} (s = -1), n < m
-
-    if (MODE == SPEC_MID && threadIdx.x < uint32_t(tq)) {   // c0 + c1 lam_d(k) per line, as k_dctg
-        const uint32_t q = a.q_off + q0 + threadIdx.x;
-        double lamv[kMaxDims] = {0, 0, 0, 0};
-        uint32_t rest = (q - a.q_off) < a.nlines ? q : a.q_off;
-        const int jlast = a.d == a.p - 1 ? a.p - 2 : a.p - 1;
-        for (int j = 0; j < a.p; ++j) {
-            if (j == a.d) continue;
-            const uint32_t qq = (j < jlast) ? a.fd[j].div(rest) : 0u;
-            lamv[j] = a.lam[a.lam_off[j] + (rest - qq * a.m[j])];
-            rest = qq;
-        }
-        double c0 = a.w0, c1 = 0.0;
-        for (int S = 1; S < (1 << a.p); ++S) {
-            if (a.cS[S] == 0.0) continue;
-            double prod = sigma * a.cS[S];
-            for (int j = 0; j < a.p; ++j)
-                if (j != a.d && ((S >> j) & 1)) prod *= lamv[j];
-            if ((S >> a.d) & 1) c1 += prod;
-            else c0 += prod;
-        }
-        lc0[threadIdx.x] = c0;
-        lc1[threadIdx.x] = c1;
-    }
-
-    auto gaddr = [&](uint32_t ql, uint32_t k) -> uint32_t {
-        const uint32_t q = q0 + ql;
-        if (D0) return q * uint32_t(m) + k;
-        const uint32_t hi = a.fds.div(q);
-        return (q - hi * a.stride) + hi * a.stride * uint32_t(m) + k * a.stride;
-    };
-    auto slot = [&](int n) { return int(__brev(uint32_t(n)) >> (32 - L)); };
-    // (complex line, sample k) of work item e: lanes over k for d = 0 (contiguous lines), over the line pairs for
-    // a strided pass (the pair's two words are adjacent, the tile's pairs one row)
-    auto item = [&](int e, int& cl, int& k) {
-        if (D0) {
-            cl = int(a.fm.div(uint32_t(e)));
-            k = e - cl * m;
-        } else {
-            cl = e & (ncl - 1);
-            k = e >> lncl;
-        }
-    };
-    auto load_pair = [&](int cl, int k) -> double2 {
-        double v[2] = {0.0, 0.0};
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const uint32_t ql = uint32_t(2 * cl + h);
-            if (q0 + ql < a.nlines) {
-                const uint32_t gi = gaddr(ql, uint32_t(k));
-                v[h] = __builtin_nontemporal_load(a.in + gi);
-                if (FORMB)
-                    v[h] += ca * __builtin_nontemporal_load(a.ga + gi) + cb * __builtin_nontemporal_load(a.gb + gi);
-            }
-        }
-        return make_double2(v[0], v[1]);
-    };
-    // zero the convolution's padding slots n in [m, M)
-    auto zero_pad = [&]() {
-        const int np = ncl * (M - m);
-        for (int e = threadIdx.x; e < np; e += dctb::NT) {
-            const int cl = e / (M - m), n = m + (e - cl * (M - m));
-            buf[cl * LP + slot(n)] = make_double2(0.0, 0.0);
-        }
-    };
-    // circular convolution of every line with b (bhat = its transform / M): bit-reversed in and out
-    auto convolve = [&](const double2* __restrict__ bhat) {
-        fft_lines<false, false>(buf, a.tw, ncl, L, LP);
-        for (int e = threadIdx.x; e < ncl * M; e += dctb::NT) {
-            const int cl = e >> L, k = e & (M - 1);
-            buf[cl * LP + k] = cmul(buf[cl * LP + k], bhat[k]);
-        }
-        __syncthreads();
-        fft_lines<true, true>(buf, a.tw, ncl, L, LP);
-    };
-
-    // ---- load: forward / MID: y[n] c[n] at slot(n), n = the Makhoul position of sample k; inverse: X[k] at slot(k)
-    const int total = ncl * m;
-    for (int e = threadIdx.x; e < total; e += dctb::NT) {
-        int cl, k;
-        item(e, cl, k);
-        const double2 v = load_pair(cl, k);
-        if (MODE == SPEC_INV) {
-            buf[cl * LP + slot(k)] = v;
-        } else {
-            const int n = (k & 1) ? m - 1 - (k >> 1) : (k >> 1);
-            buf[cl * LP + slot(n)] = cmul(v, chirp[n]);
-        }
-    }
-    if (MODE != SPEC_INV) zero_pad();
-    __syncthreads();
-    if (MODE != SPEC_INV) convolve(a.bvf);
-
-    // ---- spectrum <-> DCT coefficients over the pairs (k, m - k) (k_dctg), at their slots ------------------
-    {
-        const int half = m >> 1, npl = (m & 1) ? half + 1 : half;
-        const int npairs = ncl * npl;
-        for (int t = threadIdx.x; t < npairs; t += dctb::NT) {
-            const int line = t / npl, k = t - line * npl;
-            double2* x = buf + line * LP;
-            const bool self = k == 0;
-            const bool mid = self && !(m & 1);
-            const int ka = k, kb = self ? half : m - k;
-            const int sa = slot(ka), sb = slot(kb);
-            double2 Xk, Xmk = make_double2(0.0, 0.0);
-            if (MODE != SPEC_INV) {   // Z[k] = c[k] conv[k]
-                const double2 Z1 = cmul(x[sa], chirp[ka]), q1 = a.twq[ka];
-                if (self) {
-                    Xk = make_double2(q1.x * Z1.x, q1.x * Z1.y);
-                    if (mid) {
-                        const double2 Z2 = cmul(x[sb], chirp[kb]), q2 = a.twq[kb];
-                        Xmk = make_double2(q2.x * Z2.x, q2.x * Z2.y);
-                    }
-                } else {
-                    const double2 Z2 = cmul(x[sb], chirp[kb]), q2 = a.twq[kb];
-                    const double2 Ap = make_double2(0.5 * (Z1.x + Z2.x), 0.5 * (Z1.y - Z2.y));
-                    const double2 Bp = make_double2(0.5 * (Z1.y + Z2.y), -0.5 * (Z1.x - Z2.x));
-                    Xk = make_double2(q1.x * Ap.x - q1.y * Ap.y, q1.x * Bp.x - q1.y * Bp.y);
-                    Xmk = make_double2(q2.x * Ap.x + q2.y * Ap.y, q2.x * Bp.x + q2.y * Bp.y);
-                }
-            } else {
-                Xk = x[sa];
-                if (!self || mid) Xmk = x[sb];
-            }
-            if (MODE == SPEC_MID) {
-                const double* lamd = a.lam + a.lam_off[a.d];
-                const int l0 = 2 * line, l1 = 2 * line + 1;
-                const double la = lamd[ka];
-                Xk.x *= a.inv_n / (lc0[l0] + lc1[l0] * la);
-                Xk.y *= a.inv_n / (lc0[l1] + lc1[l1] * la);
-                if (!self || mid) {
-                    const double lb = lamd[kb];
-                    Xmk.x *= a.inv_n / (lc0[l0] + lc1[l0] * lb);
-                    Xmk.y *= a.inv_n / (lc0[l1] + lc1[l1] * lb);
-                }
-            }
-            if (MODE == SPEC_FWD) {
-                x[sa] = Xk;
-                if (!self || mid) x[sb] = Xmk;
-                continue;
-            }
-            // V[k] = conj(q[k]) (X[k] - i X[m-k]), then the inverse transform's input chirp conj c[k]
-            const double2 q2 = cconj(a.twq[kb]);
-            if (self) {
-                x[sa] = cmul(Xk, cconj(chirp[0]));
-                if (mid) {
-                    const double2 va2 = cmul(q2, make_double2(Xmk.x, -Xmk.x));
-                    const double2 vb2 = cmul(q2, make_double2(Xmk.y, -Xmk.y));
-                    x[sb] = cmul(make_double2(va2.x - vb2.y, va2.y + vb2.x), cconj(chirp[kb]));
-                }
-            } else {
-                const double2 q1 = cconj(a.twq[ka]);
-                const double2 va1 = cmul(q1, make_double2(Xk.x, -Xmk.x));
-                const double2 vb1 = cmul(q1, make_double2(Xk.y, -Xmk.y));
-                const double2 va2 = cmul(q2, make_double2(Xmk.x, -Xk.x));
-                const double2 vb2 = cmul(q2, make_double2(Xmk.y, -Xk.y));
-                x[sa] = cmul(make_double2(va1.x - vb1.y, va1.y + vb1.x), cconj(chirp[ka]));
-                x[sb] = cmul(make_double2(va2.x - vb2.y, va2.y + vb2.x), cconj(chirp[kb]));
-            }
-        }
-        if (MODE != SPEC_FWD) zero_pad();   // (disjoint from the pairs' slots)
-        __syncthreads();
-    }
-
-    if (MODE != SPEC_FWD) convolve(a.bvi);
-
-    // ---- store: forward: X[k] from slot(k); inverse / MID: sample k = conj c[n] conv[n], n its Makhoul position
-    for (int e = threadIdx.x; e < total; e += dctb::NT) {
-        int cl, k;
-        item(e, cl, k);
-        double2 v;
-        if (MODE == SPEC_FWD) {
-            v = buf[cl * LP + slot(k)];
-        } else {
-            const int n = (k & 1) ? m - 1 - (k >> 1) : (k >> 1);
-            v = cmul(buf[cl * LP + slot(n)], cconj(chirp[n]));
-        }
-        const uint32_t ql = uint32_t(2 * cl);
-        if (q0 + ql < a.nlines) __builtin_nontemporal_store(v.x, a.out + gaddr(ql, uint32_t(k)));
-        if (q0 + ql + 1 < a.nlines) __builtin_nontemporal_store(v.y, a.out + gaddr(ql + 1, uint32_t(k)));
-    }
-}
-
-// k_dctb8: the same Bluestein passes with k_dct8's register-resident radix-8 Stockham stages (stages_from) for the
-// length-M FFTs: a thread holds 8 complex values of one complex line (two real lines), LDS carries only the exchanges
-// between stages, both FFTs of a convolution leave natural order. The LDS-staged k_dctb spends ~20x the HBM bytes in
-// LDS traffic (every radix-2^2 stage a round trip through LDS for two length-M FFTs per transform) and runs at ~0.9 TB/s
-// (251^3); this keeps the working set of a stage in registers.
+// a linear convolution, evaluated as a circular one of length M = 2^ceil(log2(2m - 1)): the chirped input goes
+// through a forward FFT, the product with the transform of b (a per-dimension table, 1/M folded in) through the
+// inverse FFT. The Makhoul pairing (k, m - k), the MID divide and b formed on load are k_dctg's. Per line pair: two
+// length-M FFTs per transform (four in a MID pass); fp64 round-off grows as log M, like the planned FFTs'.
+//
+// k_dctb8 runs the length-M FFTs with k_dct8's register-resident radix-8 Stockham stages (stages_from): a thread
+// holds 8 complex values of one complex line (two real lines), LDS carries only the exchanges between stages, both
+// FFTs of a convolution leave natural order. (The first form, k_dctb, ran them with k_dct's radix-2^2 LDS FFT: every
+// stage a round trip through LDS, ~20x the HBM bytes in LDS traffic and ~0.9 TB/s at 251^3. It was removed; it last
+// existed in commit ae72d5c.)
 template <int L, int MODE, bool D0, bool FORMB, int TQW>
 __global__ __launch_bounds__((spec8::ShapeK<L, TQW>::NT)) void k_dctb8(const SpecArgs a) {
     using S = spec8::ShapeK<L, TQW>;
     constexpr int M = S::M, TPL = S::TPL, NCL = S::NCL, R0 = S::R0;
+    static_assert(D0 || !FORMB, "b is formed on load along dim 0 only");
     double sigma = a.sigma, ca = a.ca, cb = a.cb;
     if (a.skip && *a.skip) return;
     if (a.ctl) {
@@ -2391,8 +1922,6 @@ static void launch_dctb8_t(SpecArgs& a, hipStream_t s, int mode, bool d0, bool f
         if (d0) {
             if (formb) MVTV_DCTB8(SPEC_FWD, true, true);
             else MVTV_DCTB8(SPEC_FWD, true, false);
-        } else if (formb) {
-            MVTV_DCTB8(SPEC_FWD, false, true);
         } else {
             MVTV_DCTB8(SPEC_FWD, false, false);
         }
@@ -2403,8 +1932,6 @@ static void launch_dctb8_t(SpecArgs& a, hipStream_t s, int mode, bool d0, bool f
         if (d0) {
             if (formb) MVTV_DCTB8(SPEC_MID, true, true);
             else MVTV_DCTB8(SPEC_MID, true, false);
-        } else if (formb) {
-            MVTV_DCTB8(SPEC_MID, false, true);
         } else {
             MVTV_DCTB8(SPEC_MID, false, false);
         }
@@ -2428,59 +1955,18 @@ static void launch_dctb8_l(SpecArgs& a, hipStream_t s, int mode, bool d0, bool f
 }
 
 static hipError_t launch_dctb(SpecArgs& a, hipStream_t s, int mode, bool d0, bool formb) {
-    const int M = 1 << a.L;
-    if (!probe_env("MVTV_DCTB_LDS")) {   // the register-stage form (probe builds: MVTV_DCTB_LDS=1 keeps k_dctb)
-        switch (a.L) {
-            case 5: launch_dctb8_l<5>(a, s, mode, d0, formb); return hipGetLastError();
-            case 6: launch_dctb8_l<6>(a, s, mode, d0, formb); return hipGetLastError();
-            case 7: launch_dctb8_l<7>(a, s, mode, d0, formb); return hipGetLastError();
-            case 8: launch_dctb8_l<8>(a, s, mode, d0, formb); return hipGetLastError();
-            case 9: launch_dctb8_l<9>(a, s, mode, d0, formb); return hipGetLastError();
-            case 10: launch_dctb8_l<10>(a, s, mode, d0, formb); return hipGetLastError();
-            case 11: launch_dctb8_l<11>(a, s, mode, d0, formb); return hipGetLastError();
-            case 12: launch_dctb8_l<12>(a, s, mode, d0, formb); return hipGetLastError();
-            case 13: launch_dctb8_l<13>(a, s, mode, d0, formb); return hipGetLastError();
-            default: break;
-        }
+    switch (a.L) {   // M = 2^L: 11 <= m <= 4096 gives L = 5 .. 13
+        case 5: launch_dctb8_l<5>(a, s, mode, d0, formb); return hipGetLastError();
+        case 6: launch_dctb8_l<6>(a, s, mode, d0, formb); return hipGetLastError();
+        case 7: launch_dctb8_l<7>(a, s, mode, d0, formb); return hipGetLastError();
+        case 8: launch_dctb8_l<8>(a, s, mode, d0, formb); return hipGetLastError();
+        case 9: launch_dctb8_l<9>(a, s, mode, d0, formb); return hipGetLastError();
+        case 10: launch_dctb8_l<10>(a, s, mode, d0, formb); return hipGetLastError();
+        case 11: launch_dctb8_l<11>(a, s, mode, d0, formb); return hipGetLastError();
+        case 12: launch_dctb8_l<12>(a, s, mode, d0, formb); return hipGetLastError();
+        case 13: launch_dctb8_l<13>(a, s, mode, d0, formb); return hipGetLastError();
+        default: return hipErrorInvalidValue;
     }
-    // <= 16 lines in <= 64 KB of LDS (two complex lines' worth at least); M = 8192 takes one line pair in 128 KB
-    int tq = 16;
-    while (tq > 2 && size_t(tq / 2) * size_t(M + spec::PAD) * sizeof(double2) > 65536) tq /= 2;
-    a.tq = tq;
-    const size_t smem = size_t(tq / 2) * size_t(M + spec::PAD) * sizeof(double2);
-    if (smem > 160 * 1024) return hipErrorInvalidValue;
-    const dim3 grid((a.nlines + uint32_t(tq) - 1) / uint32_t(tq)), block(dctb::NT);
-#define MVTV_DCTB(MODE, D0, FB)                                                                               \
-    do {                                                                                                       \
-        if (smem > 65536)                                                                                      \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dctb<MODE, D0, FB>),                    \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, int(smem));                  \
-        klaunch(k_dctb<MODE, D0, FB>, grid, block, uint32_t(smem), s, a);                                      \
-    } while (0)
-    if (mode == SPEC_FWD) {
-        if (d0) {
-            if (formb) MVTV_DCTB(SPEC_FWD, true, true);
-            else MVTV_DCTB(SPEC_FWD, true, false);
-        } else if (formb) {
-            MVTV_DCTB(SPEC_FWD, false, true);
-        } else {
-            MVTV_DCTB(SPEC_FWD, false, false);
-        }
-    } else if (mode == SPEC_INV) {
-        if (d0) MVTV_DCTB(SPEC_INV, true, false);
-        else MVTV_DCTB(SPEC_INV, false, false);
-    } else {
-        if (d0) {
-            if (formb) MVTV_DCTB(SPEC_MID, true, true);
-            else MVTV_DCTB(SPEC_MID, true, false);
-        } else if (formb) {
-            MVTV_DCTB(SPEC_MID, false, true);
-        } else {
-            MVTV_DCTB(SPEC_MID, false, false);
-        }
-    }
-#undef MVTV_DCTB
-    return hipGetLastError();
 }
 
 // =============================================================================================
@@ -2492,172 +1978,18 @@ static hipError_t launch_dctb(SpecArgs& a, hipStream_t s, int mode, bool d0, boo
 // ~6 flops per element against two length-m FFTs, a divide and the DCT pre/post twiddles, with the
 // same 2N words of HBM traffic; the pass stops being VALU/latency bound.
 //
-// Partitioned Thomas: a thread owns SEG consecutive rows of one line and eliminates them with the
-// left / right neighbours x[lo-1] = L, x[hi+1] = R kept symbolic: x_i = G_i + H_i L + K_i R. The
-// line's Toeplitz interior makes 1/den_i, e_i, H_i, K_i the same for every segment (line constants,
-// built once per workgroup in LDS); the Neumann ends are the mirror conditions x[-1] = x[0],
-// x[m] = x[m-1]. One thread per line then solves the 2 x NSEG interface system (u_j = x at a
-// segment's first row, v_j at its last) by block elimination, and every thread finishes its rows.
-// The result is the exact solve (the system is strictly diagonally dominant: c0 > 0, c1 >= 0),
-// scaled by inv_n * m_d (the normalisation of the transforms along the other dims).
+// The line is cut into segments of SEG consecutive rows, one thread each; the Neumann ends are the mirror
+// conditions x[-1] = x[0], x[m] = x[m-1]. The result is the exact solve (the system is strictly diagonally
+// dominant: c0 > 0, c1 >= 0), scaled by inv_n * m_d (the normalisation of the transforms along the other dims).
+// (The first form, k_tri, was a partitioned Thomas elimination with the segments' neighbours kept symbolic and a
+// 2 x NSEG interface system per line; the factorised form below replaced it in round 6, DESIGN.md section 4.1. It
+// was removed and last existed in commit ae72d5c.)
 namespace tri {
 constexpr int TQ = 16;    // lines per workgroup: one 128-B row per position (d > 0)
-template <int L, int SEG, int TQL = TQ>
-struct Shape {
-    static constexpr int M = 1 << L;
-    static constexpr int NSEG = M / SEG;   // segments (threads) per line
-    static constexpr int NT = TQL * NSEG;
-};
 }  // namespace tri
 
-// TQL lines per workgroup: 16 (128-B rows) by default; 2-D meshes with few lines take 4 or 8 with the
-// tiles dealt to the XCDs in contiguous runs (a.xcd), as k_dct8's strided passes
-template <int L, int SEG, int TQL = tri::TQ>
-__global__ __launch_bounds__((tri::Shape<L, SEG, TQL>::NT)) void k_tri(const SpecArgs a) {
-    using S = tri::Shape<L, SEG, TQL>;
-    constexpr int TQ = TQL, NSEG = S::NSEG;
-    double sigma = a.sigma;
-    if (a.skip && *a.skip) return;
-    if (a.ctl) {
-        if (a.ctl->done) return;
-        sigma = a.ctl->sigma;
-    }
-    __shared__ double t_id[SEG][TQ], t_e[SEG][TQ], t_h[SEG][TQ], t_k[SEG][TQ];   // line constants
-    __shared__ double s_a[TQ];                                                    // -c1 per line
-    __shared__ double s_u[NSEG][TQ], s_v[NSEG][TQ], s_bu[NSEG][TQ], s_bv[NSEG][TQ];
-    const int t = threadIdx.x, c = t % TQ, sj = t / TQ;
-    const uint32_t bx = a.xcd ? (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3) : blockIdx.x;
-    const uint32_t q0 = bx * uint32_t(TQ);
-    const uint32_t q = q0 + uint32_t(c);
-    const bool valid = q < a.nlines;
-    const uint32_t base = (q & (a.stride - 1)) + ((q >> a.ls) << (a.ls + L)) + (uint32_t(sj * SEG) << a.ls);
-
-    // the line's eigenvalue loads are issued before the rows, so the line constants below wait for them
-    // alone (loads complete in order: issued after the rows, they would wait for all SEG row loads)
-    double lamv[kMaxDims] = {0, 0, 0, 0};
-    if (t < TQ) {
-        // c0 + c1 T along d for this line (q indexes dims 0..p-2 column-major, as k_dct8's MID)
-        const uint32_t ql = a.q_off + (valid ? q : q0);
-        uint32_t rest = ql;
-        const int jlast = a.d == a.p - 1 ? a.p - 2 : a.p - 1;
-        for (int jj = 0; jj < a.p; ++jj) {
-            if (jj == a.d) continue;
-            const uint32_t qq = (jj < jlast) ? a.fd[jj].div(rest) : 0u;
-            lamv[jj] = a.lam[a.lam_off[jj] + (rest - qq * a.m[jj])];
-            rest = qq;
-        }
-    }
-    double g[SEG];
-#pragma unroll
-    for (int i = 0; i < SEG; ++i) g[i] = valid ? __builtin_nontemporal_load(a.in + base + (uint32_t(i) << a.ls)) : 0.0;
-
-    if (t < TQ) {
-        double c0 = a.w0, c1 = 0.0;
-        for (int Sm = 1; Sm < (1 << a.p); ++Sm) {
-            if (a.cS[Sm] == 0.0) continue;
-            double prod = sigma * a.cS[Sm];
-            for (int jj = 0; jj < a.p; ++jj)
-                if (jj != a.d && ((Sm >> jj) & 1)) prod *= lamv[jj];
-            if ((Sm >> a.d) & 1) c1 += prod;
-            else c0 += prod;
-        }
-        // Thomas on one interior segment: den_i = B - A e_{i-1}, e_i = A / den_i, h_i = -A h_{i-1} / den_i
-        const double A = -c1, B = c0 + 2.0 * c1;
-        double e = 0.0, h = 1.0;
-#pragma unroll 1
-        for (int i = 0; i < SEG; ++i) {
-            const double id = 1.0 / (B - A * e);
-            e = A * id;
-            h = -A * h * id;
-            t_id[i][c] = id;
-            t_e[i][c] = e;
-            t_h[i][c] = h;
-        }
-        // back substitution of the L / R responses: H_i = h_i - e_i H_{i+1}, K_i = -e_i K_{i+1}
-        double H = t_h[SEG - 1][c], K = -t_e[SEG - 1][c];
-        t_k[SEG - 1][c] = K;
-#pragma unroll 1
-        for (int i = SEG - 2; i >= 0; --i) {
-            const double ei = t_e[i][c];
-            H = t_h[i][c] - ei * H;
-            K = -ei * K;
-            t_h[i][c] = H;
-            t_k[i][c] = K;
-        }
-        s_a[c] = A;
-    }
-    __syncthreads();
-
-    // this segment with L = R = 0: forward elimination, then back substitution
-    {
-        const double A = s_a[c];
-        g[0] *= t_id[0][c];
-#pragma unroll
-        for (int i = 1; i < SEG; ++i) g[i] = (g[i] - A * g[i - 1]) * t_id[i][c];
-#pragma unroll
-        for (int i = SEG - 2; i >= 0; --i) g[i] -= t_e[i][c] * g[i + 1];
-        s_u[sj][c] = g[0];
-        s_v[sj][c] = g[SEG - 1];
-    }
-    __syncthreads();
-
-    if (t < TQ) {
-        // interface system: u_j = G0_j + H0 L_j + K0 R_j, v_j = G1_j + H1 L_j + K1 R_j with
-        // L_j = v_{j-1} (L_0 = u_0), R_j = u_{j+1} (R_last = v_last). Eliminate forward to
-        // z_j = (au, av) + (bu, bv) u_{j+1}, solve the last 2 x 2 block, substitute back.
-        const double H0 = t_h[0][c], K0 = t_k[0][c], H1 = t_h[SEG - 1][c], K1 = t_k[SEG - 1][c];
-        double av = 0.0, bv = 0.0;   // v_{j-1} = av + bv u_j
-#pragma unroll 1
-        for (int j = 0; j < NSEG - 1; ++j) {
-            const double g0 = s_u[j][c], g1 = s_v[j][c];
-            double au, bu;
-            if (j == 0) {
-                const double id = 1.0 / (1.0 - H0);
-                au = g0 * id;
-                bu = K0 * id;
-                av = g1 + H1 * au;
-                bv = K1 + H1 * bu;
-            } else {
-                const double id = 1.0 / (1.0 - H0 * bv);
-                au = (g0 + H0 * av) * id;
-                bu = K0 * id;
-                const double nav = g1 + H1 * av + H1 * bv * au;
-                bv = K1 + H1 * bv * bu;
-                av = nav;
-            }
-            s_u[j][c] = au;
-            s_bu[j][c] = bu;
-            s_v[j][c] = av;
-            s_bv[j][c] = bv;
-        }
-        constexpr int J = NSEG - 1;
-        const double a11 = 1.0 - H0 * bv, a12 = -K0, a21 = -H1 * bv, a22 = 1.0 - K1;
-        const double b1 = s_u[J][c] + H0 * av, b2 = s_v[J][c] + H1 * av;
-        const double idet = 1.0 / (a11 * a22 - a12 * a21);
-        double u = (b1 * a22 - a12 * b2) * idet;
-        s_u[J][c] = u;
-        s_v[J][c] = (a11 * b2 - a21 * b1) * idet;
-#pragma unroll 1
-        for (int j = J - 1; j >= 0; --j) {
-            const double un = u;
-            u = s_u[j][c] + s_bu[j][c] * un;
-            s_v[j][c] = s_v[j][c] + s_bv[j][c] * un;
-            s_u[j][c] = u;
-        }
-    }
-    __syncthreads();
-
-    const double Lj = sj == 0 ? s_u[0][c] : s_v[sj - 1][c];
-    const double Rj = sj == NSEG - 1 ? s_v[NSEG - 1][c] : s_u[sj + 1][c];
-    const double sc = a.inv_n * double(S::M);
-    if (!valid) return;
-#pragma unroll
-    for (int i = 0; i < SEG; ++i)
-        __builtin_nontemporal_store(sc * (g[i] + t_h[i][c] * Lj + t_k[i][c] * Rj), a.out + base + (uint32_t(i) << a.ls));
-}
-
 // ---------------------------------------------------------------------------------------------
-// k_trir: the same line solves by the factorised operator (round 6). c0 I + c1 T is, away from the ends,
+// k_trir: the line solves by the factorised operator (round 6). c0 I + c1 T is, away from the ends,
 // -c1 x[i-1] + (c0 + 2 c1) x[i] - c1 x[i+1] = kappa (1 - r S+)(1 - r S-) with r the root in (0, 1) of
 // c1 r^2 - (c0 + 2 c1) r + c1 = 0; its Green's function is r^|k| / D with D = sqrt(c0 (c0 + 4 c1)). The
 // Neumann ends are the mirror conditions, so the line's solve is the bi-infinite one on the even extension of
@@ -2667,8 +1999,8 @@ __global__ __launch_bounds__((tri::Shape<L, SEG, TQL>::NT)) void k_tri(const Spe
 // Segment-parallel: a thread runs both recursions over its SEG rows from zero (two independent chains),
 // one thread per line combines the segments' sums into every segment's carries (F into its first row, B into
 // its last) and closes the mirror, and every thread reruns the recursions with its carries. No divide per row,
-// no per-row line constants (k_tri keeps four [SEG][TQ] tables in ~97 KB of LDS, so one workgroup fits a CU,
-// and eliminates the interface on one wave with a divide per step); LDS here is 2 sums per segment and five
+// no per-row line constants (the Thomas form kept four [SEG][TQ] tables in ~97 KB of LDS, so one workgroup fit a CU,
+// and eliminated the interface on one wave with a divide per step); LDS here is 2 sums per segment and five
 // constants per line. r = 2 c1 / (c0 + 2 c1 + D) and 1 - r = (c0 + D) / (c0 + 2 c1 + D) are cancellation-free;
 // 1 - r^k by t_2k = t_k (2 - t_k). Against a long-double Thomas solve (numpy transcription): 1e-15 at
 // c1 / c0 = 1e2, 3e-14 at 1e7 relative (an LU solve of the same system: 2e-11 at 1e7).
@@ -2806,175 +2138,14 @@ __global__ __launch_bounds__((trir::Shape<L, SEG, TQL>::NT), (SEG <= 16 ? 8 : 4)
     }
 }
 
-// k_trig: the same solve for any line length m = (NSEG - 1) * s + sr (segment length s <= SMAX chosen at launch,
-// NSEG <= NS, the last segment sr <= s rows) and any line stride (FastDiv addressing): the last-dimension pass of
-// the mixed-radix and prime-length meshes. Rows past a segment's length in the fixed-size register arrays are
-// predicated off. A shorter last segment (RG: m has no divisor in the segment range, e.g. a prime length) shares
-// the forward-elimination constants id_i, h_i (they depend on the row's distance from the segment's top only) and
-// has its own backward responses H, K (from its own last row). TQ lines per workgroup: 16 (128-B rows,
-// any block of <= 64 segments) or, where the block fits 1024 threads, 32 / 64 (256- / 512-B rows) with the segment
-// arrays sized to the block (k_tris's tiles; e_i = A id_i recomputed, not stored: the same double)
+// The general lines: the same solve for any line length m = (NSEG - 1) * s + sr (segment length s <= SMAX chosen at
+// launch, NSEG <= NS, the last segment sr <= s rows; m may have no divisor in the segment range, e.g. a prime length)
+// and any line stride (FastDiv addressing): the last-dimension pass of the mixed-radix and prime-length meshes. Rows
+// past a segment's length in the fixed-size register arrays are predicated off. TQ lines per workgroup: 16 (128-B
+// rows, any block of <= 64 segments) or, where the block fits 1024 threads, 32 / 64 (256- / 512-B rows) with the
+// segment arrays sized to the block (the slab solve's tiles)
 namespace trig {
 constexpr int SMAX = 32, NSMAX = 64, TQ = 16;
-}
-
-template <int SMAX, int TQ, int NS, bool RG = false>
-__global__ __launch_bounds__(1024) void k_trig(const SpecArgs a, int sl, int nseg, int sr) {
-    double sigma = a.sigma;
-    if (a.skip && *a.skip) return;
-    if (a.ctl) {
-        if (a.ctl->done) return;
-        sigma = a.ctl->sigma;
-    }
-    __shared__ double t_id[SMAX][TQ], t_h[SMAX][TQ], t_k[SMAX][TQ];
-    __shared__ double s_a[TQ];
-    __shared__ double s_u[NS][TQ], s_v[NS][TQ], s_bu[NS][TQ], s_bv[NS][TQ];
-    __shared__ double t_h2[RG ? SMAX : 1][TQ], t_k2[RG ? SMAX : 1][TQ];   // the last segment's H, K
-    const int t = threadIdx.x, c = t % TQ, sj = t / TQ;
-    const int ln = (RG && sj == nseg - 1) ? sr : sl;   // this thread's segment length
-    const uint32_t m = a.m[a.d];
-    const uint32_t q0 = (a.xrun ? xcd_run(blockIdx.x, gridDim.x) : blockIdx.x) * uint32_t(TQ);
-    const uint32_t q = q0 + uint32_t(c);
-    const bool valid = q < a.nlines;
-    const uint32_t qq = valid ? q : q0;
-    const uint32_t hi = a.fds.div(qq);
-    const uint32_t base = (qq - hi * a.stride) + hi * a.stride * m + uint32_t(sj * sl) * a.stride;
-
-    double g[SMAX];
-#pragma unroll
-    for (int i = 0; i < SMAX; ++i)
-        g[i] = (valid && i < ln) ? __builtin_nontemporal_load(a.in + base + uint32_t(i) * a.stride) : 0.0;
-
-    if (t < TQ) {
-        const uint32_t ql = a.q_off + qq;
-        double lamv[kMaxDims] = {0, 0, 0, 0};
-        uint32_t rest = ql;
-        const int jlast = a.d == a.p - 1 ? a.p - 2 : a.p - 1;
-        for (int jj = 0; jj < a.p; ++jj) {
-            if (jj == a.d) continue;
-            const uint32_t qd = (jj < jlast) ? a.fd[jj].div(rest) : 0u;
-            lamv[jj] = a.lam[a.lam_off[jj] + (rest - qd * a.m[jj])];
-            rest = qd;
-        }
-        double c0 = a.w0, c1 = 0.0;
-        for (int Sm = 1; Sm < (1 << a.p); ++Sm) {
-            if (a.cS[Sm] == 0.0) continue;
-            double prod = sigma * a.cS[Sm];
-            for (int jj = 0; jj < a.p; ++jj)
-                if (jj != a.d && ((Sm >> jj) & 1)) prod *= lamv[jj];
-            if ((Sm >> a.d) & 1) c1 += prod;
-            else c0 += prod;
-        }
-        const double A = -c1, B = c0 + 2.0 * c1;
-        double e = 0.0, h = 1.0;
-#pragma unroll 1
-        for (int i = 0; i < sl; ++i) {
-            const double id = 1.0 / (B - A * e);
-            e = A * id;
-            h = -A * h * id;
-            t_id[i][c] = id;
-            t_h[i][c] = h;
-        }
-        if constexpr (RG) {   // the last segment's sweep first: it reads the forward h_i that the next one replaces
-            double H2 = t_h[sr - 1][c], K2 = -(A * t_id[sr - 1][c]);
-            t_h2[sr - 1][c] = H2;
-            t_k2[sr - 1][c] = K2;
-#pragma unroll 1
-            for (int i = sr - 2; i >= 0; --i) {
-                const double ei = A * t_id[i][c];
-                H2 = t_h[i][c] - ei * H2;
-                K2 = -ei * K2;
-                t_h2[i][c] = H2;
-                t_k2[i][c] = K2;
-            }
-        }
-        double H = t_h[sl - 1][c], K = -(A * t_id[sl - 1][c]);
-        t_k[sl - 1][c] = K;
-#pragma unroll 1
-        for (int i = sl - 2; i >= 0; --i) {
-            const double ei = A * t_id[i][c];
-            H = t_h[i][c] - ei * H;
-            K = -ei * K;
-            t_h[i][c] = H;
-            t_k[i][c] = K;
-        }
-        s_a[c] = A;
-    }
-    __syncthreads();
-
-    {
-        const double A = s_a[c];
-        g[0] *= t_id[0][c];
-#pragma unroll
-        for (int i = 1; i < SMAX; ++i)
-            if (i < ln) g[i] = (g[i] - A * g[i - 1]) * t_id[i][c];
-        double last = 0.0;
-#pragma unroll
-        for (int i = SMAX - 1; i >= 0; --i) {
-            if (i == ln - 1) last = g[i];
-            if (i < ln - 1) g[i] -= (A * t_id[i][c]) * g[i + 1];
-        }
-        s_u[sj][c] = g[0];
-        s_v[sj][c] = last;
-    }
-    __syncthreads();
-
-    if (t < TQ) {
-        const double H0 = t_h[0][c], K0 = t_k[0][c], H1 = t_h[sl - 1][c], K1 = t_k[sl - 1][c];
-        double av = 0.0, bv = 0.0;
-#pragma unroll 1
-        for (int j = 0; j < nseg - 1; ++j) {
-            const double g0 = s_u[j][c], g1 = s_v[j][c];
-            double au, bu;
-            if (j == 0) {
-                const double id = 1.0 / (1.0 - H0);
-                au = g0 * id;
-                bu = K0 * id;
-                av = g1 + H1 * au;
-                bv = K1 + H1 * bu;
-            } else {
-                const double id = 1.0 / (1.0 - H0 * bv);
-                au = (g0 + H0 * av) * id;
-                bu = K0 * id;
-                const double nav = g1 + H1 * av + H1 * bv * au;
-                bv = K1 + H1 * bv * bu;
-                av = nav;
-            }
-            s_u[j][c] = au;
-            s_bu[j][c] = bu;
-            s_v[j][c] = av;
-            s_bv[j][c] = bv;
-        }
-        const int J = nseg - 1;
-        const double H0J = RG ? t_h2[0][c] : H0, K0J = RG ? t_k2[0][c] : K0;
-        const double H1J = RG ? t_h2[sr - 1][c] : H1, K1J = RG ? t_k2[sr - 1][c] : K1;
-        const double a11 = 1.0 - H0J * bv, a12 = -K0J, a21 = -H1J * bv, a22 = 1.0 - K1J;
-        const double b1 = s_u[J][c] + H0J * av, b2 = s_v[J][c] + H1J * av;
-        const double idet = 1.0 / (a11 * a22 - a12 * a21);
-        double u = (b1 * a22 - a12 * b2) * idet;
-        s_u[J][c] = u;
-        s_v[J][c] = (a11 * b2 - a21 * b1) * idet;
-#pragma unroll 1
-        for (int j = J - 1; j >= 0; --j) {
-            const double un = u;
-            u = s_u[j][c] + s_bu[j][c] * un;
-            s_v[j][c] = s_v[j][c] + s_bv[j][c] * un;
-            s_u[j][c] = u;
-        }
-    }
-    __syncthreads();
-
-    const double Lj = sj == 0 ? s_u[0][c] : s_v[sj - 1][c];
-    const double Rj = sj == nseg - 1 ? s_v[nseg - 1][c] : s_u[sj + 1][c];
-    const double sc = a.inv_n * double(m);
-    if (!valid) return;
-    const bool lastseg = RG && sj == nseg - 1;
-#pragma unroll
-    for (int i = 0; i < SMAX; ++i)
-        if (i < ln) {
-            const double h = lastseg ? t_h2[i][c] : t_h[i][c], kk = lastseg ? t_k2[i][c] : t_k[i][c];
-            __builtin_nontemporal_store(sc * (g[i] + h * Lj + kk * Rj), a.out + base + uint32_t(i) * a.stride);
-        }
 }
 
 // (r^k, 1 - r^k) pairs: products and powers keep 1 - r^k free of cancellation (1 - r^(a+b) = t_a + r^a t_b)
@@ -2992,7 +2163,7 @@ __device__ __forceinline__ PowT powt_pow(PowT x, uint32_t n) {
     return y;
 }
 
-// k_trigr: k_trir's factorised solve for k_trig's lines (any length m = (nseg - 1) sl + sr, any stride; a shorter
+// k_trigr: k_trir's factorised solve for the general lines (any length m = (nseg - 1) sl + sr, any stride; a shorter
 // last segment sr <= sl). Segment j's carries go through r^len_j; the mirror closure through r^m.
 template <int SMAX, int TQ, int NS>
 __global__ __launch_bounds__(1024) void k_trigr(const SpecArgs a, int sl, int nseg, int sr) {
@@ -3125,253 +2296,25 @@ __global__ __launch_bounds__(1024) void k_trigr(const SpecArgs a, int sl, int ns
 // Rank r holds rows [zb_r, ze_r) of every line (its owned planes). Its local block of the line's
 // operator, with the neighbours x[zb_r - 1] = L and x[ze_r] = R as unknowns (a mirror at the mesh's own
 // ends), has the solution x = G + L H + R K (G: the data with L = R = 0; H, K: the responses to L = 1 and
-// R = 1). Phase 1 (k_tris<1>) computes, per line, the first and last rows of G, H and K (6 numbers) without
-// writing the mesh; the interface system that couples the ranks' (first, last) rows of a line is solved
-// where the line's chunk lives (k_tris_iface: one thread per line, O(G)); phase 3 (k_tris<3>) solves the
-// local block again with the now known L and R and writes x. The ranks exchange 6 + 2 numbers per line
-// instead of the 2 x (owned planes) numbers per line of two transposes: at 512^3 over 8 ranks 15 MB
-// instead of 235 MB per rank per iteration. Within a rank the block is cut into nseg segments of sl rows,
-// one thread each, as k_trig (Toeplitz interior: the segment constants are line constants in LDS).
+// R = 1). Phase 1 computes, per line, what the rank's block contributes to the interface without writing the mesh;
+// the interface system that couples the ranks' (first, last) rows of a line is solved where the line's chunk lives
+// (one thread per line, O(G)); phase 3 solves the local block again with the now known neighbours and writes x.
+// The ranks exchange a few numbers per line instead of the 2 x (owned planes) numbers per line of two transposes:
+// at 512^3 over 8 ranks 15 MB (the Thomas form's 6 + 2 numbers; the factorised form below sends 2 + 2) instead of
+// 235 MB per rank per iteration. Within a rank the block is cut into nseg segments of sl rows, one thread each.
+// (The Thomas form, k_tris / k_tris_iface, was removed; it last existed in commit ae72d5c.)
 namespace tris {
 constexpr int NSMAX = 64, TQ = 16;
 }
 
-// TQ lines per workgroup (16: 128-B rows; 64: 512-B rows, one full run per wave load), NS >= nseg segments (the LDS
-// of the interface arrays is sized by it: with NS = 64 for every block, a 4-segment block of a G = 8 rank at 512^3
-// took 48 KB for one wave, 3 waves per CU, and moved 0.9-1.5 TB/s)
-template <int PHASE, int SMAX, int TQ = tris::TQ, int NS = tris::NSMAX>
-__global__ __launch_bounds__(1024) void k_tris(const SpecArgs a, int sl, int nseg, double* __restrict__ x,
-                                               double* __restrict__ coef, const double* __restrict__ lr,
-                                               uint32_t chunk, int lo_ext, int hi_ext, double scale) {
-    double sigma = a.sigma;
-    if (a.skip && *a.skip) return;
-    if (a.ctl) {
-        if (a.ctl->done) return;
-        sigma = a.ctl->sigma;
-    }
-    __shared__ double t_id[SMAX][TQ], t_h[SMAX][TQ], t_k[SMAX][TQ];   // e_i = A id_i: recomputed, not stored
-    __shared__ double s_a[TQ];
-    __shared__ double s_u[NS][TQ], s_v[NS][TQ], s_bu[NS][TQ];
-    // phase 1: the forward-eliminated u of the L- and R-response tracks; phase 3: the slopes of v_j on u_{j+1}
-    __shared__ double s_u1[PHASE == 1 ? NS : 1][TQ], s_u2[PHASE == 1 ? NS : 1][TQ], s_bv[PHASE == 3 ? NS : 1][TQ];
-    const int t = threadIdx.x, c = t % TQ, sj = t / TQ;
-    const uint32_t q0 = blockIdx.x * uint32_t(TQ);
-    const uint32_t q = q0 + uint32_t(c);
-    const bool valid = q < a.nlines;
-    const uint32_t qq = valid ? q : q0;
-    const size_t base = size_t(qq) + size_t(sj * sl) * a.stride;   // lines are contiguous: stride = plane
-
-    double g[SMAX];
-#pragma unroll
-    for (int i = 0; i < SMAX; ++i)
-        g[i] = (valid && i < sl) ? __builtin_nontemporal_load(x + base + size_t(i) * a.stride) : 0.0;
-    double lx = 0.0, rx = 0.0;   // phase 3: the neighbours' values (the interface solve's result)
-    if (PHASE == 3 && t < TQ) {
-        const uint32_t s = qq / chunk, l = qq - s * chunk;
-        if (lo_ext) lx = lr[(size_t(s) * 2) * chunk + l];
-        if (hi_ext) rx = lr[(size_t(s) * 2 + 1) * chunk + l];
-    }
-
-    if (t < TQ) {   // c0 + c1 T along the last dim for line qq (dims 0..p-2 column-major)
-        double lamv[kMaxDims] = {0, 0, 0, 0};
-        uint32_t rest = qq;
-        for (int jj = 0; jj < a.p - 1; ++jj) {
-            const uint32_t qd = (jj < a.p - 2) ? a.fd[jj].div(rest) : 0u;
-            lamv[jj] = a.lam[a.lam_off[jj] + (rest - qd * a.m[jj])];
-            rest = qd;
-        }
-        double c0 = a.w0, c1 = 0.0;
-        for (int Sm = 1; Sm < (1 << a.p); ++Sm) {
-            if (a.cS[Sm] == 0.0) continue;
-            double prod = sigma * a.cS[Sm];
-            for (int jj = 0; jj < a.p - 1; ++jj)
-                if ((Sm >> jj) & 1) prod *= lamv[jj];
-            if ((Sm >> (a.p - 1)) & 1) c1 += prod;
-            else c0 += prod;
-        }
-        const double A = -c1, B = c0 + 2.0 * c1;
-        double e = 0.0, h = 1.0;
-#pragma unroll 1
-        for (int i = 0; i < sl; ++i) {
-            const double id = 1.0 / (B - A * e);
-            e = A * id;
-            h = -A * h * id;
-            t_id[i][c] = id;
-            t_h[i][c] = h;
-        }
-        double H = t_h[sl - 1][c], K = -(A * t_id[sl - 1][c]);
-        t_k[sl - 1][c] = K;
-#pragma unroll 1
-        for (int i = sl - 2; i >= 0; --i) {
-            const double ei = A * t_id[i][c];
-            H = t_h[i][c] - ei * H;
-            K = -ei * K;
-            t_h[i][c] = H;
-            t_k[i][c] = K;
-        }
-        s_a[c] = A;
-    }
-    __syncthreads();
-
-    {   // this segment with zero neighbours
-        const double A = s_a[c];
-        g[0] *= t_id[0][c];
-#pragma unroll
-        for (int i = 1; i < SMAX; ++i)
-            if (i < sl) g[i] = (g[i] - A * g[i - 1]) * t_id[i][c];
-        double last = 0.0;
-#pragma unroll
-        for (int i = SMAX - 1; i >= 0; --i) {
-            if (i == sl - 1) last = g[i];
-            if (i < sl - 1) g[i] -= (A * t_id[i][c]) * g[i + 1];
-        }
-        s_u[sj][c] = g[0];
-        s_v[sj][c] = last;
-    }
-    __syncthreads();
-
-    if (t < TQ) {
-        // segments' interface system as k_trig, with the block's ends either the mesh's mirror (v_{-1} = u_0,
-        // R_last = v_last) or a neighbour rank's value. Eliminated forward to v_{j-1} = av + bv u_j (bv is the
-        // same for every right-hand side: phase 1 carries three, the data and the responses to L = 1, R = 1).
-        const double H0 = t_h[0][c], K0 = t_k[0][c], H1 = t_h[sl - 1][c], K1 = t_k[sl - 1][c];
-        constexpr int NR = PHASE == 1 ? 3 : 1;
-        double av[NR], bv = lo_ext ? 0.0 : 1.0;
-        av[0] = lo_ext ? lx : 0.0;
-        if constexpr (NR == 3) {
-            av[1] = lo_ext ? 1.0 : 0.0;
-            av[2] = 0.0;
-        }
-#pragma unroll 1
-        for (int j = 0; j < nseg - 1; ++j) {
-            const double id = 1.0 / (1.0 - H0 * bv);
-            const double bu = K0 * id;
-#pragma unroll
-            for (int r = 0; r < NR; ++r) {
-                const double g0 = r == 0 ? s_u[j][c] : 0.0, g1 = r == 0 ? s_v[j][c] : 0.0;
-                const double au = (g0 + H0 * av[r]) * id;
-                av[r] = g1 + H1 * av[r] + H1 * bv * au;
-                if (r == 0) s_u[j][c] = au;
-                if constexpr (NR == 3) {
-                    if (r == 1) s_u1[j][c] = au;
-                    if (r == 2) s_u2[j][c] = au;
-                }
-                if (r == 0) s_v[j][c] = av[0];
-            }
-            bv = K1 + H1 * bv * bu;
-            s_bu[j][c] = bu;
-            if constexpr (PHASE == 3) s_bv[j][c] = bv;
-        }
-        // last segment: R_J = cr v_J + Rx (mirror: cr = 1, Rx = 0; neighbour: cr = 0, Rx = its value)
-        const int J = nseg - 1;
-        const double cr = hi_ext ? 0.0 : 1.0;
-        const double a11 = 1.0 - H0 * bv, a12 = -K0 * cr, a21 = -H1 * bv, a22 = 1.0 - K1 * cr;
-        const double idet = 1.0 / (a11 * a22 - a12 * a21);
-        double uJ[NR], vJ[NR];
-#pragma unroll
-        for (int r = 0; r < NR; ++r) {
-            const double gJ0 = r == 0 ? s_u[J][c] : 0.0, gJ1 = r == 0 ? s_v[J][c] : 0.0;
-            const double rxr = r == 0 ? (hi_ext ? rx : 0.0) : (r == 2 && hi_ext ? 1.0 : 0.0);
-            const double b1 = gJ0 + H0 * av[r] + K0 * rxr, b2 = gJ1 + H1 * av[r] + K1 * rxr;
-            uJ[r] = (b1 * a22 - a12 * b2) * idet;
-            vJ[r] = (a11 * b2 - a21 * b1) * idet;
-        }
-        if constexpr (PHASE == 1) {
-            // first row of the block: back-substitute u_j = au_j + bu_j u_{j+1} down to u_0 for each track
-            double u[3] = {uJ[0], uJ[1], uJ[2]};
-#pragma unroll 1
-            for (int j = J - 1; j >= 0; --j) {
-                const double bu = s_bu[j][c];
-                u[0] = s_u[j][c] + bu * u[0];
-                u[1] = s_u1[j][c] + bu * u[1];
-                u[2] = s_u2[j][c] + bu * u[2];
-            }
-            if (valid) {   // [chunk s][6][line in chunk]: Gf Gl Hf Hl Kf Kl
-                const uint32_t s = q / chunk, l = q - s * chunk;
-                double* o = coef + size_t(s) * 6 * chunk + l;
-                o[0] = u[0];
-                o[size_t(chunk)] = vJ[0];
-                o[2 * size_t(chunk)] = u[1];
-                o[3 * size_t(chunk)] = vJ[1];
-                o[4 * size_t(chunk)] = u[2];
-                o[5 * size_t(chunk)] = vJ[2];
-            }
-        } else {
-            // every segment's (u_j, v_j) by back substitution
-            s_u[J][c] = uJ[0];
-            s_v[J][c] = vJ[0];
-            double un = uJ[0];
-#pragma unroll 1
-            for (int j = J - 1; j >= 0; --j) {
-                const double u = s_u[j][c] + s_bu[j][c] * un;
-                s_v[j][c] = s_v[j][c] + s_bv[j][c] * un;
-                s_u[j][c] = u;
-                un = u;
-            }
-        }
-    }
-    if constexpr (PHASE == 3) {
-        __shared__ double s_lx[TQ], s_rx[TQ];
-        if (t < TQ) {
-            s_lx[c] = lx;
-            s_rx[c] = rx;
-        }
-        __syncthreads();
-        const double Lj = sj == 0 ? (lo_ext ? s_lx[c] : s_u[0][c]) : s_v[sj - 1][c];
-        const double Rj = sj == nseg - 1 ? (hi_ext ? s_rx[c] : s_v[nseg - 1][c]) : s_u[sj + 1][c];
-        if (!valid) return;
-#pragma unroll
-        for (int i = 0; i < SMAX; ++i)
-            if (i < sl)
-                __builtin_nontemporal_store(scale * (g[i] + t_h[i][c] * Lj + t_k[i][c] * Rj), x + base + size_t(i) * a.stride);
-    }
-}
-
-// the interface systems of the lines of one chunk (on the rank that owns the chunk): from every rank r's
-// (Gf, Gl, Hf, Hl, Kf, Kl) [r][6][chunk] the first row u_r and last row v_r of each rank's block,
-//   u_r = Gf_r + Hf_r v_{r-1} + Kf_r u_{r+1},  v_r = Gl_r + Hl_r v_{r-1} + Kl_r u_{r+1}
-// (Hf_0 = Hl_0 = 0, Kf_{G-1} = Kl_{G-1} = 0: the mesh's ends), eliminated forward to
-// u_r = ga_r + de_r u_{r+1}, v_r = al_r + be_r u_{r+1} (kept in the input's first four rows), then
-// substituted back. Out [r][2][chunk]: (L, R) of rank r = (v_{r-1}, u_{r+1}).
-__global__ __launch_bounds__(256) void k_tris_iface(double* __restrict__ co, double* __restrict__ lr, uint32_t chunk,
-                                                    int G, const AdmmCtl* ctl, const int32_t* skip) {
-    if (ctl && ctl->done) return;
-    if (skip && *skip) return;
-    const uint32_t l = blockIdx.x * blockDim.x + threadIdx.x;
-    if (l >= chunk) return;
-    const size_t C = chunk;
-    double al = 0.0, be = 0.0;
-    for (int r = 0; r < G; ++r) {
-        double* c = co + size_t(r) * 6 * C + l;
-        const double Gf = c[0], Gl = c[C], Hf = c[2 * C], Hl = c[3 * C], Kf = c[4 * C], Kl = c[5 * C];
-        const double id = 1.0 / (1.0 - Hf * be);
-        const double ga = (Gf + Hf * al) * id, de = Kf * id;
-        const double nal = Gl + Hl * al + Hl * be * ga, nbe = Kl + Hl * be * de;
-        c[0] = ga;
-        c[C] = de;
-        c[2 * C] = nal;
-        c[3 * C] = nbe;
-        al = nal;
-        be = nbe;
-    }
-    double un = 0.0;   // u_{r+1}
-    for (int r = G - 1; r >= 0; --r) {
-        const double* c = co + size_t(r) * 6 * C + l;
-        const double u = c[0] + c[C] * un, v = c[2 * C] + c[3 * C] * un;
-        lr[(size_t(r) * 2 + 1) * C + l] = r < G - 1 ? un : 0.0;          // R of rank r
-        if (r + 1 < G) lr[(size_t(r + 1) * 2) * C + l] = v;               // L of rank r + 1
-        un = u;
-    }
-    lr[l] = 0.0;   // L of rank 0 (the mesh's end)
-}
-
-// ---------------------------------------------------------------------------------------------
 // The slab line solves by the factorised operator (round 6; k_trir's recursions F_i = f_i + r F_{i-1},
 // B_i = f_i + r B_{i+1}, x = (F + B - f) / D). A rank's block of a line enters the global recursions only through
 // two numbers: F at its last row and B at its first row, each from zero carries (phase 1). The chunk owner combines
 // the ranks' pairs with the multipliers r^n_r of the block lengths and closes the mirror (k_trisr_iface): every
 // block's carries, F into its first row and B into its last. Phase 3 reruns the block's recursions from them. Two
-// numbers per line cross the ranks each way (6 + 2 with the Thomas responses of k_tris), and no step divides per row.
+// numbers per line cross the ranks each way (6 + 2 with the Thomas responses), and no step divides per row.
+// TQ lines per workgroup (16: 128-B rows; 64: 512-B rows, one full run per wave load), NS >= nseg segments (the LDS
+// of the segment sums is sized by it)
 template <int PHASE, int SMAX, int TQ = tris::TQ, int NS = tris::NSMAX>
 __global__ __launch_bounds__(1024) void k_trisr(const SpecArgs a, int sl, int nseg, double* __restrict__ x,
                                                 double* __restrict__ coef, const double* __restrict__ lr,
@@ -4297,15 +3240,6 @@ bool tri_slab_ok(uint32_t n) {
     return n >= 1 && sl <= 32 && nseg <= tris::NSMAX;
 }
 
-static bool tris_thomas() {   // probe builds: MVTV_TRI_IIR=0 keeps the Thomas form (k_tris, 6 + 2 numbers per line)
-    static const bool th = [] {
-        const char* e = probe_env("MVTV_TRI_IIR");
-        return e && std::atoi(e) == 0;
-    }();
-    return th;
-}
-int tri_slab_ncoef() { return tris_thomas() ? 6 : 2; }
-
 hipError_t launch_tri_slab(const SpecPlan& sp, const Geom& og, hipStream_t s, int phase, double* x, double* coef,
                            const double* lr, uint32_t chunk, int lo_ext, int hi_ext, double scale,
                            const AdmmCtl* ctl, double sigma, double w0, const int32_t* skip) {
@@ -4335,7 +3269,6 @@ hipError_t launch_tri_slab(const SpecPlan& sp, const Geom& og, hipStream_t s, in
     // 64-line tiles with the segment arrays sized to the block (<= 16 segments: <= 1024 threads) where the lines
     // fill >= 128 such workgroups; otherwise 16-line tiles sized for any block (<= 64 segments)
     static const bool wide_off = probe_env("MVTV_TRIS_NARROW") != nullptr;
-    const bool thomas = tris_thomas();
     auto go = [&](auto kern, uint32_t tq) {
         klaunch(kern, dim3((a.nlines + tq - 1) / tq), dim3(tq * uint32_t(nseg)), 0, s, a, sl, nseg, x, coef, lr, chunk,
                 lo_ext, hi_ext, scale);
@@ -4346,36 +3279,31 @@ hipError_t launch_tri_slab(const SpecPlan& sp, const Geom& og, hipStream_t s, in
         // <= 16 planes: a 4-D rank at G = 8) size the line constants for 4
         const int ns = nseg <= 4 ? 4 : (nseg <= 8 ? 8 : 16);
         if (sl <= 4 && ns == 4) {
-            if (phase == 1) return thomas ? go(k_tris<1, 4, 64, 4>, 64u) : go(k_trisr<1, 4, 64, 4>, 64u);
-            return thomas ? go(k_tris<3, 4, 64, 4>, 64u) : go(k_trisr<3, 4, 64, 4>, 64u);
+            if (phase == 1) return go(k_trisr<1, 4, 64, 4>, 64u);
+            return go(k_trisr<3, 4, 64, 4>, 64u);
         }
         if (sl <= 16) {
             if (phase == 1) {
-                if (ns == 4) return thomas ? go(k_tris<1, 16, 64, 4>, 64u) : go(k_trisr<1, 16, 64, 4>, 64u);
-                if (ns == 8) return thomas ? go(k_tris<1, 16, 64, 8>, 64u) : go(k_trisr<1, 16, 64, 8>, 64u);
-                return thomas ? go(k_tris<1, 16, 64, 16>, 64u) : go(k_trisr<1, 16, 64, 16>, 64u);
+                if (ns == 4) return go(k_trisr<1, 16, 64, 4>, 64u);
+                if (ns == 8) return go(k_trisr<1, 16, 64, 8>, 64u);
+                return go(k_trisr<1, 16, 64, 16>, 64u);
             }
-            if (ns == 4) return thomas ? go(k_tris<3, 16, 64, 4>, 64u) : go(k_trisr<3, 16, 64, 4>, 64u);
-            if (ns == 8) return thomas ? go(k_tris<3, 16, 64, 8>, 64u) : go(k_trisr<3, 16, 64, 8>, 64u);
-            return thomas ? go(k_tris<3, 16, 64, 16>, 64u) : go(k_trisr<3, 16, 64, 16>, 64u);
+            if (ns == 4) return go(k_trisr<3, 16, 64, 4>, 64u);
+            if (ns == 8) return go(k_trisr<3, 16, 64, 8>, 64u);
+            return go(k_trisr<3, 16, 64, 16>, 64u);
         }
     }
     const uint32_t tq = uint32_t(tris::TQ);
-    if (phase == 1 && sl <= 16) return thomas ? go(k_tris<1, 16>, tq) : go(k_trisr<1, 16>, tq);
-    if (phase == 1) return thomas ? go(k_tris<1, 32>, tq) : go(k_trisr<1, 32>, tq);
-    if (sl <= 16) return thomas ? go(k_tris<3, 16>, tq) : go(k_trisr<3, 16>, tq);
-    return thomas ? go(k_tris<3, 32>, tq) : go(k_trisr<3, 32>, tq);
+    if (phase == 1 && sl <= 16) return go(k_trisr<1, 16>, tq);
+    if (phase == 1) return go(k_trisr<1, 32>, tq);
+    if (sl <= 16) return go(k_trisr<3, 16>, tq);
+    return go(k_trisr<3, 32>, tq);
 }
-
 
 hipError_t launch_tri_iface(const SpecPlan& sp, const Geom& og, hipStream_t s, double* coef_in, double* lr_out,
                             uint32_t chunk, int G, int rank, uint32_t mg, const AdmmCtl* ctl, double sigma, double w0,
                             const int32_t* skip) {
     if (G < 1 || chunk == 0) return hipErrorInvalidValue;
-    if (tris_thomas()) {
-        klaunch(k_tris_iface, dim3((chunk + 255) / 256), dim3(256), 0, s, coef_in, lr_out, chunk, G, ctl, skip);
-        return hipGetLastError();
-    }
     SpecArgs a{};
     a.ctl = ctl;
     a.skip = skip;
@@ -4394,7 +3322,7 @@ hipError_t launch_tri_iface(const SpecPlan& sp, const Geom& og, hipStream_t s, d
     return hipGetLastError();
 }
 
-// segment length for k_trig: the smallest divisor of m in [16, 32], else the largest in [4, 16),
+// segment length for k_trigr: the smallest divisor of m in [16, 32], else the largest in [4, 16),
 // with at most 64 segments; else (no such divisor: a prime length, 2 x a prime ...; probe builds keep the
 // Bluestein MID pass with MVTV_TRIG_EXACT=1) 16 rows (32 past 1024 points; m / 4 rounded up below 64 points) with a
 // shorter last segment; 0 when there is none (m < 8, m > 2048)
@@ -4416,24 +3344,17 @@ static int trig_seg(uint32_t m) {
     return m > 1024 ? 32 : 16;
 }
 
-// k_trig's tile: 64 / 32 lines (512- / 256-B rows) with the segment arrays sized to the block where it fits 1024
+// k_trigr's tile: 64 / 32 lines (512- / 256-B rows) with the segment arrays sized to the block where it fits 1024
 // threads and the lines fill >= 256 such workgroups, else 16 lines for any block (round 4's form; probe builds:
-// MVTV_TRIG_NARROW=1). sr < sl: a shorter last segment (RG)
+// MVTV_TRIG_NARROW=1). sr < sl: a shorter last segment
 static void launch_trig(const SpecArgs& a, hipStream_t s, int sl, int nseg, int sr) {
     static const bool narrow = probe_flag("MVTV_TRIG_NARROW");
     auto go = [&](auto kern, uint32_t tq) {
         klaunch(kern, dim3((a.nlines + tq - 1) / tq), dim3(tq * uint32_t(nseg)), 0, s, a, sl, nseg, sr);
     };
-    // the factorised solve (k_trigr, round 6) unless a probe build asks for k_trig (MVTV_TRI_IIR=0)
-    static const bool thomas = [] {
-        const char* e = probe_env("MVTV_TRI_IIR");
-        return e && std::atoi(e) == 0;
-    }();
 #define MVTV_TRIG(SM, TQ, NS)                                                                                   \
     do {                                                                                                        \
-        if (!thomas) go(k_trigr<SM, TQ, NS>, uint32_t(TQ));                                                     \
-        else if (sr != sl) go(k_trig<SM, TQ, NS, true>, uint32_t(TQ));                                          \
-        else go(k_trig<SM, TQ, NS, false>, uint32_t(TQ));                                                       \
+        go(k_trigr<SM, TQ, NS>, uint32_t(TQ));                                                                  \
         return;                                                                                                 \
     } while (0)
     if (!narrow) {
@@ -4460,7 +3381,7 @@ static void launch_trig(const SpecArgs& a, hipStream_t s, int sl, int nseg, int 
 #undef MVTV_TRIG
 }
 
-// k_tri serves the last-dimension pass when the lines are long enough for >= 4 segments and short enough
+// The line solve serves the last-dimension pass when the lines are long enough for >= 4 segments and short enough
 // for <= 64 (16 rows per segment up to 1024 points, 32 at 2048), the stride holds the tile's lines, and
 // either 16-line tiles fill the chip (>= 256 workgroups: 3-D and 4-D meshes) or, for the few 2048-point
 // lines of a 2-D mesh, 8-line tiles in XCD runs (2048^2: 4844 -> 5145 ADMM it/s on one box; at 1024^2 the
@@ -4468,160 +3389,67 @@ static void launch_trig(const SpecArgs& a, hipStream_t s, int sl, int nseg, int 
 // the factorised line solve (k_trir): 1024- and 512-point lines take it too, on 4-line tiles (one box, two reps each,
 // profiles/r06/v8_tri2d: 1024^2 12928 / 12925 -> 14312 / 14249 ADMM it/s, 512^2 18185 / 18166 -> 20543 / 20357; 8-line
 // tiles 14173 / 20397; 2048^2 keeps 8-line tiles: 6279 / 6226, 4-line 5319).
-// Probe builds: MVTV_DCT_TRI2D=0 / 4 / 8 forces the 2-D choice.
+// Probe builds: MVTV_DCT_TRI2D=0 keeps the FFT pass on 2-D meshes (the other tiles of that A/B, 8 lines at 512 / 1024
+// and 4 at 2048, were removed; they last existed in commit ae72d5c).
 static int tri_tiles(const SpecArgs& a, int mode, bool formb) {
     if (mode != SPEC_MID || a.d == 0 || formb) return 0;
     const char* e = probe_env("MVTV_DCT_TRI");
     if (e && std::atoi(e) == 0) return 0;
     if (a.L < 6 || a.L > 11 || a.stride < 4u) return 0;
     if (a.L <= 10 && a.stride >= uint32_t(tri::TQ) && a.nlines / uint32_t(tri::TQ) >= 256u) return tri::TQ;
-    static const int t2d_env = [] {
+    static const bool t2d_off = [] {
         const char* v = probe_env("MVTV_DCT_TRI2D");
-        return v ? std::atoi(v) : -1;
+        return v && std::atoi(v) == 0;
     }();
-    const int t2d = t2d_env >= 0 ? t2d_env : (a.L == 11 ? 8 : (a.L >= 9 ? 4 : 0));
-    if (t2d != 4 && t2d != 8) return 0;
+    const int t2d = t2d_off ? 0 : (a.L == 11 ? 8 : (a.L >= 9 ? 4 : 0));
+    if (t2d == 0) return 0;
     if (uint32_t(t2d) > a.stride || (a.nlines / uint32_t(t2d)) % 8u != 0u) return 0;
     return t2d;
 }
 
-template <int SEG, int TQL>
-static void launch_tri_seg(SpecArgs& a, hipStream_t s) {
-    const dim3 grid((a.nlines + uint32_t(TQL) - 1) / uint32_t(TQL));
-    switch (a.L) {
-        case 6: klaunch(k_tri<6, SEG, TQL>, grid, dim3(tri::Shape<6, SEG, TQL>::NT), 0, s, a); break;
-        case 7: klaunch(k_tri<7, SEG, TQL>, grid, dim3(tri::Shape<7, SEG, TQL>::NT), 0, s, a); break;
-        case 8: klaunch(k_tri<8, SEG, TQL>, grid, dim3(tri::Shape<8, SEG, TQL>::NT), 0, s, a); break;
-        case 9: klaunch(k_tri<9, SEG, TQL>, grid, dim3(tri::Shape<9, SEG, TQL>::NT), 0, s, a); break;
-        case 10: klaunch(k_tri<10, SEG, TQL>, grid, dim3(tri::Shape<10, SEG, TQL>::NT), 0, s, a); break;
-    }
-}
-
-template <int L, int SEG, int TQL>
-static bool launch_trir_l(SpecArgs& a, hipStream_t s) {
-    if constexpr (trir::Shape<L, SEG, TQL>::NT <= 1024 && trir::Shape<L, SEG, TQL>::NSEG >= 2) {
-        klaunch(k_trir<L, SEG, TQL>, dim3((a.nlines + uint32_t(TQL) - 1) / uint32_t(TQL)),
-                dim3(trir::Shape<L, SEG, TQL>::NT), 0, s, a);
-        return true;
-    }
-    return false;
-}
-
-template <int SEG, int TQL>
-static bool launch_trir_seg(SpecArgs& a, hipStream_t s) {
-    if (a.stride < uint32_t(TQL)) return false;
-    a.tq = TQL;
-    a.xcd = 0;
-    switch (a.L) {
-        case 6: return launch_trir_l<6, SEG, TQL>(a, s);
-        case 7: return launch_trir_l<7, SEG, TQL>(a, s);
-        case 8: return launch_trir_l<8, SEG, TQL>(a, s);
-        case 9: return launch_trir_l<9, SEG, TQL>(a, s);
-        case 10: return launch_trir_l<10, SEG, TQL>(a, s);
-    }
-    return false;
-}
-
-// The last-dimension pass of 3-D / 4-D meshes (16-line tiles in tri_tiles) by the factorised line solve. Tiles, where
-// the lines fill >= 256 workgroups of 64: 64 lines (512-B rows per wave load) of 32-row segments up to 256-point lines
-// (256 / 512 threads), 32 lines of 16-row segments (1024 threads, 64 VGPRs: two workgroups a CU) at 512, 32 lines of
-// 32-row segments at 1024; 16 lines of 16-row segments otherwise. Against k_tri (round 6, one box, kernel trace,
-// profiles/r06/v1_trir): 512^3 441 -> 392 us, 256^3 73 -> 49 us, 128^4 948 -> 797 us. Probe builds: MVTV_TRI_IIR=0
-// takes k_tri, "SEG,TQ" forces a tile.
-static bool launch_trir(SpecArgs& a, hipStream_t s) {
-    static const int cfg = [] {
-        const char* e = probe_env("MVTV_TRI_IIR");
-        if (!e) return -1;
-        int sg = 0, tq = 0;
-        if (std::sscanf(e, "%d,%d", &sg, &tq) != 2) return 0;
-        return sg * 1000 + tq;
-    }();
-    switch (cfg) {
-        case -1: break;
-        case 32064: return launch_trir_seg<32, 64>(a, s);
-        case 16064: return launch_trir_seg<16, 64>(a, s);
-        case 16032: return launch_trir_seg<16, 32>(a, s);
-        case 32032: return launch_trir_seg<32, 32>(a, s);
-        case 32016: return launch_trir_seg<32, 16>(a, s);
-        case 16016: return launch_trir_seg<16, 16>(a, s);
-        default: return false;
-    }
-    if (a.nlines / 64u >= 256u && a.stride >= 64u) {
-        if (a.L <= 8) return launch_trir_seg<32, 64>(a, s);
-        if (a.L == 9) return launch_trir_seg<16, 32>(a, s);
-        return launch_trir_seg<32, 32>(a, s);
-    }
-    return launch_trir_seg<16, 16>(a, s);
-}
-
-static void launch_tri(SpecArgs& a, hipStream_t s, int tq) {
-    a.tq = tq;
-    if (tq == tri::TQ && launch_trir(a, s)) return;
-    a.tq = tq;
-    a.xcd = 0;
+// The line solves of tri_tiles. tq = 16, the last-dimension pass of 3-D / 4-D meshes. Tiles, where the lines fill
+// >= 256 workgroups of 64: 64 lines (512-B rows per wave load) of 32-row segments up to 256-point lines (256 / 512
+// threads), 32 lines of 16-row segments (1024 threads, 64 VGPRs: two workgroups a CU) at 512, 32 lines of 32-row
+// segments at 1024; 16 lines of 16-row segments otherwise. Against the Thomas form (round 6, one box, kernel trace,
+// profiles/r06/v1_trir): 512^3 441 -> 392 us, 256^3 73 -> 49 us, 128^4 948 -> 797 us. tq = 4 / 8, the few lines of a
+// 2-D mesh: narrow tiles in XCD runs (grid a multiple of 8), 2048-point lines in 64 segments of 32 rows, else 16-row
+// segments.
+static hipError_t launch_tri(SpecArgs& a, hipStream_t s, int tq) {
+    // (the line stride is a power of two >= the tile here, and nlines a multiple of it: whole tiles)
+#define MVTV_TRIR(LL, SEG, TQL)                                                                                 \
+    do {                                                                                                        \
+        a.tq = TQL;                                                                                             \
+        klaunch(k_trir<LL, SEG, TQL>, dim3((a.nlines + uint32_t(TQL) - 1) / uint32_t(TQL)),                     \
+                dim3(trir::Shape<LL, SEG, TQL>::NT), 0, s, a);                                                  \
+        return hipGetLastError();                                                                               \
+    } while (0)
     if (tq == tri::TQ) {
         a.xcd = 0;
-        static const int seg = [] {
-            const char* e = probe_env("MVTV_TRI_SEG");
-            return e && std::atoi(e) == 32 ? 32 : 16;
-        }();
-        // 64 lines of 32-row segments per workgroup (512-B rows: one full run per load instruction of a wave) where
-        // the lines fill >= 256 such workgroups: 512^3 k_tri ~0.49 -> ~0.44 ms, 170.1 / 170.5 -> 171.8 / 172.0 ADMM it/s
-        // on one box (profiles/r04/v18_tri64). Probe builds: MVTV_TRI_TQ=16 / 32 force the 16- / 32-line tiles.
-        static const int tqw = [] {
-            const char* e = probe_env("MVTV_TRI_TQ");
-            return e ? std::atoi(e) : 64;
-        }();
-        if (tqw == 32 && seg == 16 && a.stride >= 32u) {
-            a.tq = 32;
-            launch_tri_seg<16, 32>(a, s);
-        } else if (tqw == 64 && seg == 16 && a.stride >= 64u && a.L >= 7 && a.L <= 9 && a.nlines / 64u >= 256u) {
-            a.tq = 64;
-            const dim3 grid((a.nlines + 63u) / 64u);
-            if (a.L == 7) klaunch(k_tri<7, 32, 64>, grid, dim3(tri::Shape<7, 32, 64>::NT), 0, s, a);
-            else if (a.L == 8) klaunch(k_tri<8, 32, 64>, grid, dim3(tri::Shape<8, 32, 64>::NT), 0, s, a);
-            else klaunch(k_tri<9, 32, 64>, grid, dim3(tri::Shape<9, 32, 64>::NT), 0, s, a);
-        } else if (seg == 32) {
-            launch_tri_seg<32, tri::TQ>(a, s);
-        } else {
-            launch_tri_seg<16, tri::TQ>(a, s);
+        if (a.nlines / 64u >= 256u && a.stride >= 64u) {
+            switch (a.L) {
+                case 6: MVTV_TRIR(6, 32, 64);
+                case 7: MVTV_TRIR(7, 32, 64);
+                case 8: MVTV_TRIR(8, 32, 64);
+                case 9: MVTV_TRIR(9, 16, 32);
+                case 10: MVTV_TRIR(10, 32, 32);
+            }
+            return hipErrorInvalidValue;
         }
-        return;
-    }
-    a.xcd = 1;   // 2-D: narrow tiles in XCD runs (grid a multiple of 8, tri_tiles)
-    const dim3 grid(a.nlines / uint32_t(tq));
-    static const bool thomas = [] {
-        const char* e = probe_env("MVTV_TRI_IIR");
-        return e && std::atoi(e) == 0;
-    }();
-    if (!thomas) {   // the factorised solve (k_trir): 2048-point lines in 64 segments of 32 rows, else 16-row segments
-        if (a.L == 11) {
-            if (tq == 4) klaunch(k_trir<11, 32, 4>, grid, dim3(trir::Shape<11, 32, 4>::NT), 0, s, a);
-            else klaunch(k_trir<11, 32, 8>, grid, dim3(trir::Shape<11, 32, 8>::NT), 0, s, a);
-            return;
+        switch (a.L) {
+            case 6: MVTV_TRIR(6, 16, 16);
+            case 7: MVTV_TRIR(7, 16, 16);
+            case 8: MVTV_TRIR(8, 16, 16);
+            case 9: MVTV_TRIR(9, 16, 16);
+            case 10: MVTV_TRIR(10, 16, 16);
         }
-        switch (a.L * 16 + tq) {
-            case 6 * 16 + 4: klaunch(k_trir<6, 16, 4>, grid, dim3(trir::Shape<6, 16, 4>::NT), 0, s, a); return;
-            case 6 * 16 + 8: klaunch(k_trir<6, 16, 8>, grid, dim3(trir::Shape<6, 16, 8>::NT), 0, s, a); return;
-            case 7 * 16 + 4: klaunch(k_trir<7, 16, 4>, grid, dim3(trir::Shape<7, 16, 4>::NT), 0, s, a); return;
-            case 7 * 16 + 8: klaunch(k_trir<7, 16, 8>, grid, dim3(trir::Shape<7, 16, 8>::NT), 0, s, a); return;
-            case 8 * 16 + 4: klaunch(k_trir<8, 16, 4>, grid, dim3(trir::Shape<8, 16, 4>::NT), 0, s, a); return;
-            case 8 * 16 + 8: klaunch(k_trir<8, 16, 8>, grid, dim3(trir::Shape<8, 16, 8>::NT), 0, s, a); return;
-            case 9 * 16 + 4: klaunch(k_trir<9, 16, 4>, grid, dim3(trir::Shape<9, 16, 4>::NT), 0, s, a); return;
-            case 9 * 16 + 8: klaunch(k_trir<9, 16, 8>, grid, dim3(trir::Shape<9, 16, 8>::NT), 0, s, a); return;
-            case 10 * 16 + 4: klaunch(k_trir<10, 16, 4>, grid, dim3(trir::Shape<10, 16, 4>::NT), 0, s, a); return;
-            case 10 * 16 + 8: klaunch(k_trir<10, 16, 8>, grid, dim3(trir::Shape<10, 16, 8>::NT), 0, s, a); return;
-            default: break;
-        }
+        return hipErrorInvalidValue;
     }
-    if (a.L == 11) {   // 2048-point lines: 64 segments of 32 rows
-        if (tq == 4) klaunch(k_tri<11, 32, 4>, grid, dim3(tri::Shape<11, 32, 4>::NT), 0, s, a);
-        else klaunch(k_tri<11, 32, 8>, grid, dim3(tri::Shape<11, 32, 8>::NT), 0, s, a);
-    } else if (tq == 4) {
-        launch_tri_seg<16, 4>(a, s);
-    } else {
-        launch_tri_seg<16, 8>(a, s);
-    }
+    a.xcd = 1;
+    if (tq == 4 && a.L == 9) MVTV_TRIR(9, 16, 4);
+    if (tq == 4 && a.L == 10) MVTV_TRIR(10, 16, 4);
+    if (tq == 8 && a.L == 11) MVTV_TRIR(11, 32, 8);
+#undef MVTV_TRIR
+    return hipErrorInvalidValue;
 }
 
 // ------------------------------------------------------------------------------ launcher
@@ -4650,8 +3478,6 @@ static void launch_dct8_tile(SpecArgs& a, hipStream_t s, int mode, bool d0, bool
         if (d0) {
             if (formb) MVTV_DCT8(SPEC_FWD, true, true);
             else MVTV_DCT8(SPEC_FWD, true, false);
-        } else if (formb) {   // the first pass of a k_march solve (dim 2 first)
-            MVTV_DCT8(SPEC_FWD, false, true);
         } else {
             MVTV_DCT8(SPEC_FWD, false, false);
         }
@@ -4732,9 +3558,7 @@ static void launch_dct8(SpecArgs& a, hipStream_t s, int mode, bool d0, bool form
 
 // the fused in-plane passes (k_plane8): m0 = m1 = 2^L, 16 <= m <= 128, dims 0 and 1 transformed first
 bool plane_pass_ok(const Geom& g) {
-    if (g.p < 3 || g.m[0] != g.m[1] || probe_env("MVTV_PLANE_OFF") || probe_env("MVTV_DCT_LDS") ||
-        probe_env("MVTV_DCT_MID"))
-        return false;
+    if (g.p < 3 || g.m[0] != g.m[1] || probe_env("MVTV_PLANE_OFF") || probe_env("MVTV_DCT_LDS")) return false;
     // and enough planes to fill the chip: 128^3's 128 planes (one workgroup each) ran 1 % slower than the two
     // passes, 128^4's 16384 3.5 % faster per ADMM iteration (profiles/r03/v15_plane)
     const uint32_t m = g.m[0];
@@ -4789,59 +3613,6 @@ hipError_t launch_plane_pass(const SpecPlan& sp, const Geom& g, hipStream_t s, i
         default: return hipErrorInvalidValue;
     }
 #undef MVTV_PLANE
-    return hipGetLastError();
-}
-
-// 3-D meshes whose dim-0 lines are 256 - 2048 points (a power of two) and enough dim-2 planes to fill the chip:
-// dim 2 first, then the marching dim-0 transform + dim-1 tridiagonal passes (k_march). Probe builds only
-// (MVTV_MARCH=1): it moves 9N words per solve instead of 11N, but its two dim-2 passes stride 2 MB (the first one
-// reading three inputs) and run slower than the dim-0 / dim-1 passes they replace, and the march itself, one
-// workgroup per dim-2 plane (8 waves per CU at 512^3), reaches 3.7 TB/s: 512^3 162.5-163.4 ADMM it/s against
-// 165.1-165.8 for the five-pass solve, 165.2-166.4 with 32-line strided tiles, 256^3 1150 against 1170, same
-// process, interleaved (profiles/r04/v2_march).
-bool march_ok(const Geom& g) {
-    const char* on = probe_env("MVTV_MARCH");
-    if (!on || std::atoi(on) == 0) return false;
-    if (g.p != 3 || probe_env("MVTV_DCT_LDS") || probe_env("MVTV_DCT_MID")) return false;
-    const uint32_t m0 = g.m[0];
-    if (m0 < 256 || m0 > 2048 || (m0 & (m0 - 1)) != 0) return false;
-    const uint32_t nr = 2u * (2048u / m0);
-    return g.m[1] % nr == 0 && g.m[2] >= 128 && g.m[2] <= 4096;
-}
-
-hipError_t launch_march(const SpecPlan& sp, const Geom& g, hipStream_t s, bool bwd, double* x, double sigma, double w0,
-                        const AdmmCtl* ctl, const int32_t* skip) {
-    if (!march_ok(g)) return hipErrorInvalidValue;
-    SpecArgs a{};
-    a.ctl = ctl;
-    a.skip = skip;
-    a.in = x;
-    a.out = x;
-    a.tw = reinterpret_cast<const double2*>(sp.tw + sp.tw_off[0]);
-    a.twq = reinterpret_cast<const double2*>(sp.twq + sp.twq_off[0]);
-    a.lam = sp.lam;
-    for (int j = 0; j < kMaxDims; ++j) {
-        a.lam_off[j] = sp.lam_off[j];
-        a.m[j] = g.m[j];
-    }
-    for (int S = 0; S < 16; ++S) a.cS[S] = g.cS[S];
-    a.sigma = sigma;
-    a.w0 = w0;
-    a.inv_n = 1.0 / double(g.N);
-    const dim3 grid(g.m[2]), block(256);
-#define MVTV_MARCH(LL)                                                                                         \
-    do {                                                                                                       \
-        if (bwd) klaunch(k_march<LL, true>, grid, block, 0, s, a, g.m[1]);                                     \
-        else klaunch(k_march<LL, false>, grid, block, 0, s, a, g.m[1]);                                        \
-    } while (0)
-    switch (g.m[0]) {
-        case 256: MVTV_MARCH(8); break;
-        case 512: MVTV_MARCH(9); break;
-        case 1024: MVTV_MARCH(10); break;
-        case 2048: MVTV_MARCH(11); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef MVTV_MARCH
     return hipGetLastError();
 }
 
@@ -5085,6 +3856,7 @@ __device__ __forceinline__ uint32_t dsp_addr(const SplitArgs& s, uint32_t q, uin
 
 template <bool INV, bool D0, bool FORMB>
 __global__ __launch_bounds__(dctg::NT) void k_dsc(const SplitArgs s) {
+    static_assert(D0 || !FORMB, "b is formed on load along dim 0 only");
     double ca = s.ca, cb = s.cb;
     if (s.skip && *s.skip) return;
     if (s.ctl) {
@@ -5392,9 +4164,8 @@ static hipError_t launch_dct_split(const SpecPlan& sp, const Geom& g, hipStream_
             if (formb) go(k_dsc<false, true, true>, gridc, smc, true);
             else go(k_dsc<false, true, false>, gridc, smc, true);
             go(k_dsr<false, true>, gridr, smr, false);
-        } else {
-            if (formb) go(k_dsc<false, false, true>, gridc, smc, true);
-            else go(k_dsc<false, false, false>, gridc, smc, true);
+        } else {   // (b is formed on load along dim 0 only: launch_dct_pass)
+            go(k_dsc<false, false, false>, gridc, smc, true);
             go(k_dsr<false, false>, gridr, smr, false);
         }
     } else if (d0) {
@@ -5500,6 +4271,7 @@ __device__ __forceinline__ void chirp_el(const ChirpArgs& s, uint32_t e, uint32_
 
 template <bool INV, bool D0, bool FORMB>
 __global__ __launch_bounds__(dctg::NT) void k_chc(const ChirpArgs s) {
+    static_assert(D0 || !FORMB, "b is formed on load along dim 0 only");
     double ca = s.ca, cb = s.cb;
     if (s.skip && *s.skip) return;
     if (s.ctl) {
@@ -5744,9 +4516,8 @@ static hipError_t launch_dct_chirp(const SpecPlan& sp, const Geom& g, hipStream_
         if (d0) {
             if (formb) go(k_chc<false, true, true>, gridc, smc, 0);
             else go(k_chc<false, true, false>, gridc, smc, 0);
-        } else {
-            if (formb) go(k_chc<false, false, true>, gridc, smc, 0);
-            else go(k_chc<false, false, false>, gridc, smc, 0);
+        } else {   // (b is formed on load along dim 0 only: launch_dct_pass)
+            go(k_chc<false, false, false>, gridc, smc, 0);
         }
         go(k_chr, gridr, smr, 1);
         if (d0) go(k_cho<false, true>, gridc, smc, 2);
@@ -5777,6 +4548,7 @@ hipError_t launch_dct_pass(const SpecPlan& sp, const Geom& g, hipStream_t s, int
                            const double* ga, double ca, const double* gb, double cb, double* out, double sigma,
                            double w0, const AdmmCtl* ctl, uint32_t q_off, double inv_n, const int32_t* skip,
                            const PcgFuse* pf, bool fold) {
+    if (ga != nullptr && d != 0) return hipErrorInvalidValue;   // b is formed on load along dim 0 only
     SpecArgs a{};
     a.ctl = ctl;
     a.skip = skip;
@@ -5863,7 +4635,7 @@ hipError_t launch_dct_pass(const SpecPlan& sp, const Geom& g, hipStream_t s, int
         const bool trig_lines = a.nlines / uint32_t(trig::TQ) >= 256u || (!trig_few_off && a.nlines >= 1000u);
         if (mode == SPEC_MID && d > 0 && !formb && trig_lines && !probe_env("MVTV_DCT_TRI0")) {
             int sl = trig_seg(m);
-            // more than 16 segments keep k_trig on 32-line tiles; where 64-line tiles fill the chip, <= 32-row
+            // more than 16 segments keep k_trigr on 32-line tiles; where 64-line tiles fill the chip, <= 32-row
             // segments with a shorter last one bring it to 16 (500: 25 x 20 -> 15 x 32 + 20 rows, 0.69 -> 0.48 ms
             // at 500^3, profiles/r05/v13_trig_sl32; probe builds: MVTV_TRIG_SL forces, MVTV_TRIG_NARROW keeps)
             static const bool sl_forced = probe_env("MVTV_TRIG_SL") != nullptr;
@@ -5876,7 +4648,7 @@ hipError_t launch_dct_pass(const SpecPlan& sp, const Geom& g, hipStream_t s, int
                 return hipGetLastError();
             }
         }
-        if (!planned) {   // Bluestein (k_dctb): L = log2 M, the length-M twiddles
+        if (!planned) {   // Bluestein (k_dctb8): L = log2 M, the length-M twiddles
             const double2* t = reinterpret_cast<const double2*>(sp.blu + sp.blu_off[d]);
             a.L = 0;
             while ((1u << a.L) < sp.blu_M[d]) ++a.L;
@@ -5897,10 +4669,7 @@ hipError_t launch_dct_pass(const SpecPlan& sp, const Geom& g, hipStream_t s, int
         launch_dctg(a, s, mode, d == 0, formb);
         return hipGetLastError();
     }
-    if (const int tq = tri_tiles(a, mode, formb)) {
-        launch_tri(a, s, tq);
-        return hipGetLastError();
-    }
+    if (const int tq = tri_tiles(a, mode, formb)) return launch_tri(a, s, tq);
     if (a.L >= 3 && !probe_env("MVTV_DCT_LDS")) {
         switch (a.L) {
             case 3: launch_dct8<3>(a, s, mode, d == 0, formb); break;

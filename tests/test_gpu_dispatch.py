@@ -22,8 +22,8 @@ long-double Thomas solve at c1 / c0 = 1e7 where well-conditioned lines sit at 1e
 about 30 that belongs to the algorithm. b = randn + 2: the mean passes through the solve unchanged, so max|x_ld| is
 at least |mean b|, about 2, at every sigma and a relative bound is meaningful.
 
-Instantiations no release build reaches (probe_env only) have no case: k_tri, k_trig, k_dctb, k_march, the
-MVTV_TRI_IIR="SEG,TQ" tiles, k_trir<L, 16, 8>, k_trir<L <= 8, 16, 4>, k_trir<11, 32, 4>, k_dctm<.., 8>.
+The instantiations no release build could reach (probe_env only: the Thomas-form line solves, k_dctb, k_march, the
+forced k_trir tiles, k_dctm<.., 8>) had no case and were removed from the library.
 Release-reachable ones without a case are listed in DESIGN.md §2 with the reason (they need more than 2^24 nodes, or
 a CPU reference run of tens of seconds).
 """
