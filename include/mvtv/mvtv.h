@@ -210,6 +210,32 @@ mvtv_status mvtv_admm_run(mvtv_problem* prob, const mvtv_admm_opts* opts, double
 mvtv_status mvtv_path(mvtv_problem* prob, const mvtv_admm_opts* opts, const double* lambdas, int32_t n_lambda,
                       const double* theta_init, double rho_init, double* thetas_out, double* rhos_out,
                       mvtv_admm_stats* stats);
+/* Batched small-mesh fits: nbatch independent paths on the problem's mesh in one call, each member run start to
+ * finish by one workgroup with no host in its ADMM loop (variant B, u0 = 0; theta-solve: Jacobi-PCG on W + rho D^T D,
+ * warm-started, the stopping rule of MVTV_SOLVER_PCG). prob supplies only the geometry (p, m, deltas, block order,
+ * weights), the device and the stream; its own data and resident state are not touched. A member's result does not
+ * depend on its position in the batch or on the batch size.
+ * mvtv_problem_batch_ok: 1 when the mesh is admitted: not a slab rank, N <= 4096 for p <= 3, N <= 1296 for p = 4.
+ * Members are member-major in every array; (theta, u, rho) are carried from each lambda to the next per member, as
+ * mvtv_path does, and the next lambda starts once every member has finished the current one. n_lambda = 1 is the
+ * batched single fit. Honoured options: fixed_iters, tol, max_counter, pcg_rtol, pcg_max_iter, pcg_strict.
+ * MVTV_BAD_ARG (before any launch) for: a mesh that is not admitted; a variant other than MVTV_VARIANT_RCPP; a
+ * theta_solver other than AUTO or PCG; a non-NaN opts.sigma; nbatch < 1 or n_lambda < 1; a lambda < 0; a rho_init that is
+ * not positive and finite; a member whose W has a negative entry or no positive one. stats[b, l] holds that member's own iters, status, norms, eps, rho and
+ * PCG counts (theta_solver = MVTV_SOLVER_PCG; seconds: the call's wall time). Returns MVTV_MAXITER when some (member,
+ * lambda) hit max_counter (the others are unaffected), MVTV_PCG_NOT_CONVERGED under pcg_strict likewise. */
+int32_t mvtv_problem_batch_ok(const mvtv_problem* prob);
+mvtv_status mvtv_path_batch(mvtv_problem* prob, const mvtv_admm_opts* opts, int32_t nbatch,
+                            const double* oty,        /* [nbatch x N] */
+                            const double* wdiag,      /* [nbatch x N], or NULL: W = I for every member */
+                            const double* lambdas,    /* [nbatch x n_lambda], member-major */
+                            int32_t n_lambda,
+                            const double* theta_init, /* [nbatch x N] */
+                            const double* rho_init,   /* [nbatch] */
+                            double* thetas_out,       /* [nbatch x n_lambda x N], may be NULL */
+                            double* u_out,            /* [nbatch x E], u after the last lambda in the problem's D row order, may be NULL */
+                            double* rhos_out,         /* [nbatch x n_lambda], may be NULL */
+                            mvtv_admm_stats* stats);  /* [nbatch x n_lambda], may be NULL */
 /* fitted values O theta for n points given their mesh index (fill_output_mbs_one, rcpp…/solvers.cpp:73) */
 mvtv_status mvtv_fitted(mvtv_problem* prob, const int64_t* mesh_index, int64_t n, double* fitted);
 

@@ -93,6 +93,9 @@ SIGNATURES = {
     "mvtv_admm_run": (C.c_int, [C.c_void_p, C.POINTER(AdmmOpts), C.c_double, C.POINTER(AdmmStats)]),
     "mvtv_path": (C.c_int, [C.c_void_p, C.POINTER(AdmmOpts), _dp, C.c_int32, _dp, C.c_double, _dp, _dp,
                             C.POINTER(AdmmStats)]),
+    "mvtv_problem_batch_ok": (C.c_int32, [C.c_void_p]),
+    "mvtv_path_batch": (C.c_int, [C.c_void_p, C.POINTER(AdmmOpts), C.c_int32, _dp, _dp, _dp, C.c_int32, _dp, _dp,
+                                  _dp, _dp, _dp, C.POINTER(AdmmStats)]),
     "mvtv_fitted": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int64, _dp]),
     "mvtv_nearest": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int64, C.POINTER(C.c_int64)]),
     "mvtv_problem_set_scattered": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int64, _dp, C.POINTER(C.c_int64)]),
@@ -288,6 +291,35 @@ class Problem:
         if s not in (MVTV_OK, MVTV_MAXITER):
             _check(s)
         return thetas, rhos, [sts[i].as_dict() for i in range(n)]
+
+    def batch_ok(self) -> bool:
+        """True when path_batch admits this mesh (mvtv_problem_batch_ok)."""
+        return bool(lib().mvtv_problem_batch_ok(self._h))
+
+    def path_batch(self, oty, lambdas, theta_init, rho_init, wdiag=None, want_thetas=True, want_u=False, **opts):
+        """Many independent variant-B paths on this mesh in one call, each member's ADMM loop run by one workgroup
+        (mvtv_path_batch). oty, theta_init [B x N]; lambdas [B x n] (or [n], shared by every member); rho_init [B];
+        wdiag [B x N] or None (W = I). Returns (thetas [B x n x N] or None, u [B x E] after the last lambda or None,
+        rhos [B x n], stats [B][n], status): status is MVTV_MAXITER when some (member, lambda) hit max_counter."""
+        o = default_opts(opts.pop("variant", VARIANT_RCPP), **opts)
+        oty = np.ascontiguousarray(np.asarray(oty, dtype=np.float64).reshape(-1, self.N))
+        B = oty.shape[0]
+        lam = np.atleast_1d(np.asarray(lambdas, dtype=np.float64))
+        lam = np.ascontiguousarray(np.broadcast_to(lam, (B, lam.shape[-1])) if lam.ndim == 1
+                                   else lam.reshape(B, lam.shape[-1]))
+        n = lam.shape[1]
+        th0 = _f64(theta_init, B * self.N)
+        rho0 = _f64(rho_init, B)
+        w = None if wdiag is None else _f64(wdiag, B * self.N)
+        thetas = np.empty((B, n, self.N)) if want_thetas else None
+        u = np.empty((B, self.E)) if want_u else None
+        rhos = np.empty((B, n))
+        sts = (AdmmStats * max(B * n, 1))()
+        s = lib().mvtv_path_batch(self._h, C.byref(o), B, _ptr(oty), _ptr(w), _ptr(lam), n, _ptr(th0), _ptr(rho0),
+                                  _ptr(thetas), _ptr(u), _ptr(rhos), sts)
+        if s not in (MVTV_OK, MVTV_MAXITER):
+            _check(s)
+        return thetas, u, rhos, [[sts[b * n + i].as_dict() for i in range(n)] for b in range(B)], s
 
     def fitted(self, mesh_index):
         idx = np.ascontiguousarray(np.asarray(mesh_index, dtype=np.int64).ravel())

@@ -2009,6 +2009,170 @@ mvtv_status mvtv_path(mvtv_problem* P, const mvtv_admm_opts* opts, const double*
     return worst;
 }
 
+int32_t mvtv_problem_batch_ok(const mvtv_problem* P) { return P && !P->slab && small_ok(P->g) ? 1 : 0; }
+
+// Many independent fits on the problem's mesh, each member's whole path in one workgroup (mvtv_small.hip). The lambda
+// loop is here: per lambda the launches of k_admm_small are enqueued two at a time and the device counter of members
+// that have not finished that lambda is read after each pair.
+mvtv_status mvtv_path_batch(mvtv_problem* P, const mvtv_admm_opts* opts, int32_t nbatch, const double* oty,
+                            const double* wdiag, const double* lambdas, int32_t n_lambda, const double* theta_init,
+                            const double* rho_init, double* thetas_out, double* u_out, double* rhos_out,
+                            mvtv_admm_stats* stats) {
+    if (!P || !opts || !oty || !lambdas || !theta_init || !rho_init) return fail(MVTV_BAD_ARG, "null argument");
+    const auto t0 = std::chrono::steady_clock::now();
+    const mvtv_admm_opts& o = *opts;
+    if (!mvtv_problem_batch_ok(P))
+        return fail(MVTV_BAD_ARG, "batched fits need one GPU's whole mesh of at most 4096 nodes (p = 4: 1296)");
+    if (o.variant != MVTV_VARIANT_RCPP) return fail(MVTV_BAD_ARG, "batched fits run variant B only");
+    if (o.theta_solver != MVTV_SOLVER_AUTO && o.theta_solver != MVTV_SOLVER_PCG)
+        return fail(MVTV_BAD_ARG, "batched fits solve for theta by PCG");
+    if (!std::isnan(o.sigma)) return fail(MVTV_BAD_ARG, "batched fits take the matrix scalar rho (sigma must be NaN)");
+    if (nbatch < 1 || n_lambda < 1) return fail(MVTV_BAD_ARG, "nbatch and n_lambda must be >= 1");
+    const size_t N = P->g.N, nbN = size_t(P->g.nb) * N, B = size_t(nbatch), NL = size_t(n_lambda);
+    for (size_t i = 0; i < B * NL; ++i)
+        if (!(lambdas[i] >= 0.0)) return fail(MVTV_BAD_ARG, "lambda must be >= 0");
+    for (size_t b = 0; b < B; ++b)
+        if (!(rho_init[b] > 0.0) || std::isinf(rho_init[b])) return fail(MVTV_BAD_ARG, "rho_init must be positive and finite");
+    if (wdiag)
+        for (size_t b = 0; b < B; ++b) {
+            bool pos = false;
+            for (size_t i = 0; i < N; ++i) {
+                if (!(wdiag[b * N + i] >= 0.0)) return fail(MVTV_BAD_ARG, "W must be >= 0");
+                pos = pos || wdiag[b * N + i] > 0.0;
+            }
+            if (!pos) return fail(MVTV_BAD_ARG, "a member's W has no positive entry");
+        }
+    DeviceGuard dg(P->device);
+    // the call's own device buffers, released on every return path
+    struct Bufs {
+        std::vector<void*> v;
+        ~Bufs() {
+            for (void* p : v) (void)hipFree(p);
+        }
+    } bufs;
+    auto dev = [&](auto** ptr, size_t n) -> mvtv_status {
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(ptr), std::max<size_t>(n, 1) * sizeof(**ptr)));
+        bufs.v.push_back(*ptr);
+        return MVTV_OK;
+    };
+    double *d_oty = nullptr, *d_w = nullptr, *d_lam = nullptr, *d_theta = nullptr, *d_z = nullptr, *d_gag = nullptr,
+           *d_thetas = nullptr;
+    SmallCtl *d_ctl = nullptr, *d_log = nullptr;
+    int32_t* d_rem = nullptr;
+    MVTV_TRY(dev(&d_oty, B * N));
+    if (wdiag) MVTV_TRY(dev(&d_w, B * N));
+    MVTV_TRY(dev(&d_lam, B * NL));
+    MVTV_TRY(dev(&d_theta, B * N));
+    MVTV_TRY(dev(&d_z, B * nbN));
+    MVTV_TRY(dev(&d_gag, B * 2 * N));
+    if (thetas_out) MVTV_TRY(dev(&d_thetas, B * NL * N));
+    MVTV_TRY(dev(&d_ctl, B));
+    MVTV_TRY(dev(&d_log, B * NL));
+    MVTV_TRY(dev(&d_rem, NL));
+    std::vector<SmallCtl> ctl(B);
+    for (size_t b = 0; b < B; ++b) {
+        ctl[b] = SmallCtl{};
+        ctl[b].cur_l = -1;
+        ctl[b].rho = rho_init[b];
+        ctl[b].c = 1.0;   // u0 = 0: z = 0, t_z = 0
+    }
+    const std::vector<int32_t> rem(NL, nbatch);
+    hipStream_t s = P->stream;
+    HIP_TRY(hipMemcpyAsync(d_oty, oty, B * N * sizeof(double), hipMemcpyHostToDevice, s));
+    if (wdiag) HIP_TRY(hipMemcpyAsync(d_w, wdiag, B * N * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_lam, lambdas, B * NL * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_theta, theta_init, B * N * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(d_z, 0, B * nbN * sizeof(double), s));
+    HIP_TRY(hipMemcpyAsync(d_ctl, ctl.data(), B * sizeof(SmallCtl), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_rem, rem.data(), NL * sizeof(int32_t), hipMemcpyHostToDevice, s));
+
+    Geom g = P->g;
+    g.eaos = 0;
+    SmallArgs a{};
+    a.oty = d_oty, a.wdiag = d_w, a.lambdas = d_lam, a.theta = d_theta, a.z = d_z, a.gag = d_gag;
+    a.ctl = d_ctl, a.log = d_log, a.thetas_out = d_thetas, a.remaining = d_rem;
+    a.n_lambda = n_lambda;
+    a.fixed_iters = o.fixed_iters;
+    a.max_counter = variant_maxc(o);
+    a.pcg_maxit = o.pcg_max_iter > 0 ? o.pcg_max_iter : 20000;
+    a.pcg_strict = o.pcg_strict;
+    a.tol = variant_tol(o);
+    const double rtol = o.pcg_rtol > 0 ? o.pcg_rtol : 1e-10;
+    a.rtol2 = rtol * rtol;
+    a.sqrtN = std::sqrt(double(N));
+    a.sqrtE = std::sqrt(double(P->E));
+    for (int k = 0; k < P->g.nb; ++k) a.sp[k] = P->sprime[k];
+    // launches that can be needed for one lambda: the iteration bound in chunks, and the pair's second
+    const int64_t it_cap = o.fixed_iters > 0 ? o.fixed_iters : a.max_counter;
+    const int64_t launch_cap = (it_cap + kSmallChunk - 1) / kSmallChunk + 2;
+    for (int32_t li = 0; li < n_lambda; ++li) {
+        a.li = li;
+        int32_t left = nbatch;
+        for (int64_t done = 0; left > 0; done += 2) {
+            if (done >= launch_cap) return fail(MVTV_HIP_ERROR, "batched fits: members unfinished after the iteration bound");
+            HIP_TRY(launch_admm_small(g, s, nbatch, a));
+            HIP_TRY(launch_admm_small(g, s, nbatch, a));
+            HIP_TRY(hipMemcpyAsync(&left, d_rem + li, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+        }
+    }
+    std::vector<SmallCtl> log(B * NL);
+    HIP_TRY(hipMemcpyAsync(log.data(), d_log, B * NL * sizeof(SmallCtl), hipMemcpyDeviceToHost, s));
+    if (thetas_out) HIP_TRY(hipMemcpyAsync(thetas_out, d_thetas, B * NL * N * sizeof(double), hipMemcpyDeviceToHost, s));
+    std::vector<double> z;
+    if (u_out) {
+        z.resize(B * nbN);
+        HIP_TRY(hipMemcpyAsync(z.data(), d_z, B * nbN * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    if (u_out) {   // u = -c clamp(z, t_z) on the real edges, blocks in the problem's order, each a column-major reduced grid
+        double* out = u_out;
+        for (size_t b = 0; b < B; ++b) {
+            const SmallCtl& c = log[b * NL + NL - 1];
+            for (int k = 0; k < P->g.nb; ++k) {
+                uint32_t rd[kMaxDims] = {1, 1, 1, 1};
+                for (int j = 0; j < P->g.p; ++j) rd[j] = P->g.m[j] - ((P->sprime[k] >> j) & 1);
+                const double* zk = z.data() + b * nbN + size_t(k) * N;
+                for (uint32_t c3 = 0; c3 < rd[3]; ++c3)
+                    for (uint32_t c2 = 0; c2 < rd[2]; ++c2)
+                        for (uint32_t c1 = 0; c1 < rd[1]; ++c1)
+                            for (uint32_t c0 = 0; c0 < rd[0]; ++c0) {
+                                const size_t i = size_t(c0) * P->g.stride[0] + size_t(c1) * P->g.stride[1] +
+                                                 size_t(c2) * P->g.stride[2] + size_t(c3) * P->g.stride[3];
+                                const double cl = std::min(std::max(zk[i], -c.t_z), c.t_z);
+                                *out++ = cl == 0.0 ? 0.0 : -c.c * cl;
+                            }
+            }
+        }
+    }
+    const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    mvtv_status worst = MVTV_OK;
+    for (size_t i = 0; i < B * NL; ++i) {
+        const SmallCtl& c = log[i];
+        if (c.status == MVTV_PCG_NOT_CONVERGED) worst = MVTV_PCG_NOT_CONVERGED;
+        else if (c.status == MVTV_MAXITER && worst == MVTV_OK) worst = MVTV_MAXITER;
+        if (rhos_out) rhos_out[i] = c.rho;
+        if (stats) {
+            mvtv_admm_stats S{};
+            S.iters = c.it;
+            S.status = c.status;
+            S.r_norm = c.primal;
+            S.s_norm = c.dual;
+            S.eps_pri = c.eps_p;
+            S.eps_dual = c.eps_d;
+            S.rho = c.rho;
+            S.pcg_iters = c.pcg_iters;
+            S.pcg_iters_max = c.pcg_max;
+            S.pcg_unconverged = c.pcg_unconv;
+            S.seconds = seconds;
+            S.theta_solver = MVTV_SOLVER_PCG;
+            stats[i] = S;
+        }
+    }
+    if (worst == MVTV_PCG_NOT_CONVERGED) fail(worst, "PCG hit pcg_max_iter");
+    return worst;
+}
+
 mvtv_status mvtv_fitted(mvtv_problem* P, const int64_t* mesh_index, int64_t n, double* fitted) {
     if (!P || (n > 0 && (!mesh_index || !fitted))) return fail(MVTV_BAD_ARG, "null argument");
     if (n == 0) return MVTV_OK;

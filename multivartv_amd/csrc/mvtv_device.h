@@ -53,4 +53,58 @@ __device__ __forceinline__ void block_reduce_store(double (&v)[NR], double* __re
     }
 }
 
+// 3^p stencil coefficients of D^T D (mvtv_kernels.hip make_stencil), passed to kernels by value
+struct StencilK {
+    double K[81];
+};
+StencilK make_stencil(const Geom& g);
+
+// Jacobi diagonal of W + sigma * sum_S cS[S] (x)_{j in S} L_j at a node with multi-index c:
+// the 1-D Neumann Laplacian's diagonal is (c > 0) + (c < m - 1).
+template <int P, int WM>
+__device__ __forceinline__ double jacobi_diag(const Geom& g, double sigma, const double* __restrict__ wdiag,
+                                              uint32_t i, const uint32_t (&c)[kMaxDims]) {
+    double l[P];
+#pragma unroll
+    for (int j = 0; j < P; ++j) l[j] = double(c[j] > 0) + double(c[j] + 1 < g.m[j]);
+    double acc = 0.0;
+#pragma unroll
+    for (int S = 1; S < (1 << P); ++S) {
+        double prod = g.cS[S];
+#pragma unroll
+        for (int j = 0; j < P; ++j)
+            if ((S >> j) & 1) prod *= l[j];
+        acc += prod;
+    }
+    double wv = (WM == W_DIAG) ? wdiag[i] : (WM == W_IDENTITY ? 1.0 : 0.0);
+    return wv + sigma * acc;
+}
+
+// K-weighted 3^P-point stencil with per-dimension clamped neighbours: (D^T D x)_i.
+template <int P>
+__device__ __forceinline__ double stencil_DtD(const Geom& g, const double* __restrict__ x, uint32_t i,
+                                              const uint32_t (&c)[kMaxDims], const double* __restrict__ K) {
+    int32_t lo[P], hi[P];
+#pragma unroll
+    for (int j = 0; j < P; ++j) {
+        lo[j] = c[j] > 0 ? -int32_t(g.stride[j]) : 0;
+        hi[j] = c[j] + 1 < g.m[j] ? int32_t(g.stride[j]) : 0;
+    }
+    double acc = 0.0;
+    constexpr int NT = (P == 1) ? 3 : (P == 2) ? 9 : (P == 3) ? 27 : 81;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        int32_t off = 0;
+        int tt = t;
+#pragma unroll
+        for (int j = 0; j < P; ++j) {
+            const int o = tt % 3;
+            tt /= 3;
+            off += (o == 0) ? lo[j] : (o == 2 ? hi[j] : 0);
+        }
+        acc = fma(K[t], x[int64_t(i) + off], acc);
+    }
+    return acc;
+}
+
 }  // namespace mvtv

@@ -468,6 +468,47 @@ hipError_t launch_gather4a_ghost(const Geom& g, int order, hipStream_t s, const 
                                  const AdmmCtl* ctl);
 hipError_t launch_gather_index(hipStream_t s, const double* theta, const int64_t* idx, int64_t n, double* out);
 
+// ---- batched small-mesh fits (mvtv_small.hip, mvtv_path_batch) ---------------------------------------------
+// One workgroup runs the whole variant-B loop of one batch member: k_admm_small<P, NT, ZLDS>, grid = members.
+// A launch runs at most kSmallChunk ADMM iterations of every unfinished member; the state (theta, z, D^T alpha,
+// D^T u, SmallCtl) round-trips through HBM between launches.
+constexpr int kSmallChunk = 32;
+constexpr uint32_t kSmallMaxN = 4096;    // admitted nodes, p <= 3 (four nodes a thread at NT = 1024)
+constexpr uint32_t kSmallMaxN4 = 1296;   // admitted nodes, p = 4 (6^4: two nodes a thread, a 16-corner butterfly each)
+constexpr uint32_t kSmallZLds = 14336;   // edge words nb * N kept in LDS (112 KiB); beyond: the member's HBM scratch
+// workgroup size from the node count: tiny meshes share a CU
+inline int small_nt(uint32_t N) { return N <= 256 ? 64 : (N <= 1024 ? 256 : 1024); }
+inline bool small_zlds(int nb, uint32_t N) { return uint64_t(nb) * N <= kSmallZLds; }
+inline bool small_ok(const Geom& g) { return g.N <= (g.p == 4 ? kSmallMaxN4 : kSmallMaxN); }
+// dynamic LDS of a launch: the neighbour-read vector [N], two reduction buffers [NT / 64][3], z [nb][N] when in LDS
+inline size_t small_lds_bytes(const Geom& g) {
+    return (size_t(g.N) + 2u * size_t(small_nt(g.N) / 64) * 3u + (small_zlds(g.nb, g.N) ? size_t(g.nb) * g.N : 0u)) *
+           sizeof(double);
+}
+// a member's control block; a copy per (member, lambda) is left in SmallArgs::log when the member finishes that lambda
+struct SmallCtl {
+    int32_t cur_l, done, status, it, counter, pcg_max, pcg_unconv, pad;
+    int64_t pcg_iters;
+    double rho, c, t_z, lambda;   // u = -c clamp(z, t_z)
+    double dual, primal, eps_d, eps_p;
+};
+struct SmallArgs {
+    const double* oty;       // [nbatch][N]
+    const double* wdiag;     // [nbatch][N] or nullptr (W = I)
+    const double* lambdas;   // [nbatch][n_lambda]
+    double* theta;           // [nbatch][N]
+    double* z;               // [nbatch][nb][N], padded block-major
+    double* gag;             // [nbatch][2][N]: D^T alpha, D^T u of an unfinished member
+    SmallCtl* ctl;           // [nbatch]
+    SmallCtl* log;           // [nbatch][n_lambda]
+    double* thetas_out;      // [nbatch][n_lambda][N] or nullptr
+    int32_t* remaining;      // [n_lambda]: members that have not finished lambda l
+    int32_t n_lambda, li, fixed_iters, max_counter, pcg_maxit, pcg_strict;
+    double tol, rtol2, sqrtN, sqrtE;
+    int32_t sp[kMaxBlocks];  // S' mask per block
+};
+hipError_t launch_admm_small(const Geom& g, hipStream_t s, int nbatch, const SmallArgs& a);
+
 // scattered-data setup (mvtv_scatter.hip)
 // axes_host_span[j] = axis_j[last] - axis_j[0] (host values; only the first guess of the bracket)
 hipError_t launch_nearest(hipStream_t s, int p, const uint32_t* m, const double* axes, const double* axes_host_span,

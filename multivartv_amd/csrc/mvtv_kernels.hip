@@ -31,54 +31,6 @@ void launch_log_push(const void* fn, dim3 grid, dim3 block) {
     r.block[0] = block.x, r.block[1] = block.y, r.block[2] = block.z;
 }
 
-// Jacobi diagonal of W + sigma * sum_S cS[S] (x)_{j in S} L_j at a node with multi-index c:
-// the 1-D Neumann Laplacian's diagonal is (c > 0) + (c < m - 1).
-template <int P, int WM>
-__device__ __forceinline__ double jacobi_diag(const Geom& g, double sigma, const double* __restrict__ wdiag,
-                                              uint32_t i, const uint32_t (&c)[kMaxDims]) {
-    double l[P];
-#pragma unroll
-    for (int j = 0; j < P; ++j) l[j] = double(c[j] > 0) + double(c[j] + 1 < g.m[j]);
-    double acc = 0.0;
-#pragma unroll
-    for (int S = 1; S < (1 << P); ++S) {
-        double prod = g.cS[S];
-#pragma unroll
-        for (int j = 0; j < P; ++j)
-            if ((S >> j) & 1) prod *= l[j];
-        acc += prod;
-    }
-    double wv = (WM == W_DIAG) ? wdiag[i] : (WM == W_IDENTITY ? 1.0 : 0.0);
-    return wv + sigma * acc;
-}
-
-// K-weighted 3^P-point stencil with per-dimension clamped neighbours: (D^T D x)_i.
-template <int P>
-__device__ __forceinline__ double stencil_DtD(const Geom& g, const double* __restrict__ x, uint32_t i,
-                                              const uint32_t (&c)[kMaxDims], const double* __restrict__ K) {
-    int32_t lo[P], hi[P];
-#pragma unroll
-    for (int j = 0; j < P; ++j) {
-        lo[j] = c[j] > 0 ? -int32_t(g.stride[j]) : 0;
-        hi[j] = c[j] + 1 < g.m[j] ? int32_t(g.stride[j]) : 0;
-    }
-    double acc = 0.0;
-    constexpr int NT = (P == 1) ? 3 : (P == 2) ? 9 : (P == 3) ? 27 : 81;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        int32_t off = 0;
-        int tt = t;
-#pragma unroll
-        for (int j = 0; j < P; ++j) {
-            const int o = tt % 3;
-            tt /= 3;
-            off += (o == 0) ? lo[j] : (o == 2 ? hi[j] : 0);
-        }
-        acc = fma(K[t], x[int64_t(i) + off], acc);
-    }
-    return acc;
-}
-
 // --------------------------------------------------------------------- edge update
 // z_new = D theta - u_old; alpha = soft(z_new, t_new); r = alpha - D theta.
 // Reductions: |r|^2, |D theta|^2, |alpha|^2 and (DTH) max |theta - theta_old|.
@@ -253,10 +205,6 @@ __global__ __launch_bounds__(kThreads) void k_edges_fill_valid(Geom g, double* _
 }
 
 // --------------------------------------------------------------------- theta-solve (Jacobi-PCG)
-struct StencilK {
-    double K[81];
-};
-
 template <int P, int WM, bool DOT, bool CHECK>
 __global__ __launch_bounds__(kThreads) void k_apply_A(Geom g, StencilK sk, double sigma,
                                                       const double* __restrict__ wdiag,
@@ -722,8 +670,6 @@ __global__ void k_gather_index(const double* __restrict__ theta, const int64_t* 
 }
 
 // --------------------------------------------------------------------- host launchers
-namespace {
-
 StencilK make_stencil(const Geom& g) {
     // K(o) = sum_S cS[S] prod_j f_j, f_j = (j in S) ? (o_j == 0 ? 2 : -1) : (o_j == 0 ? 1 : 0);
     // offsets o_j in {-1, 0, +1} are encoded base-3 as (0 -> -1, 1 -> 0, 2 -> +1), dim 0 least significant.
@@ -747,6 +693,8 @@ StencilK make_stencil(const Geom& g) {
     }
     return sk;
 }
+
+namespace {
 
 template <class F>
 hipError_t dispatch_p(int p, F&& f) {

@@ -136,7 +136,7 @@ def assign(n_items: int, world: int, rank: int):
 
 
 def mbs_impl(data, y, m, mesh=None, n_lambda=100, ftrue=None, lambdas=None, folds=1, verbose=False, seed=0,
-             device=None, group=None, _runner=None, concurrent=1):
+             device=None, group=None, _runner=None, concurrent=1, batched=False):
     """rcpp…/solvers.cpp:305-376. Returns the reference's result list as a dict (rank 0; other
     ranks return only 'cv.mses' and 'lambda_minmse_ind').
 
@@ -145,6 +145,11 @@ def mbs_impl(data, y, m, mesh=None, n_lambda=100, ftrue=None, lambdas=None, fold
 
     ``concurrent``: work items of this rank run at once, each on its own problem (HIP stream) and host
     thread; the items are independent, so results do not depend on it.
+
+    ``batched``: this rank's work items (the final path and its folds) run as one ``Problem.path_batch`` call, each
+    item a batch member with its own O^T y, W, theta_0 = mean of its y and rho_0 = lambda_0 / 5, its whole path run by
+    one workgroup. Everything after the paths is unchanged. ValueError when the mesh is not admitted
+    (``Problem.batch_ok``) or ``_runner`` is given; ``concurrent`` is ignored.
     """
     data = np.asarray(data, dtype=np.float64)
     if data.ndim == 1:
@@ -175,6 +180,8 @@ def mbs_impl(data, y, m, mesh=None, n_lambda=100, ftrue=None, lambdas=None, fold
             state["P"] = P
         return P, idx
 
+    if batched and _runner is not None:
+        raise ValueError("batched=True runs the library's own paths; _runner cannot replace them")
     if lambdas is None or _runner is None:
         P, idx_full = problem_for(data, y)
         LAMBDAS = create_lambdas(n_lambda, P, lambdas)
@@ -210,6 +217,38 @@ def mbs_impl(data, y, m, mesh=None, n_lambda=100, ftrue=None, lambdas=None, fold
     mse_mat = np.zeros((nl, max(folds, 1)))
     final = None
 
+    if batched:
+        if not P.batch_ok():
+            P.close()
+            raise ValueError(f"batched=True needs a mesh of at most 4096 nodes (p = 4: 1296), got m = {m}")
+        mine = assign(n_items, world, rank)
+        members = []   # (item, nearest mesh node per training point, O^T y, W, theta_0)
+        for item in mine:
+            tr = slice(None) if item == 0 else foldinds != item - 1
+            x, yy = data[tr], y[tr]
+            idx = P.nearest(AXES, x) if AXES is not None else nearest_index(x, MESH)
+            W, oty = interp_weights(idx, P.N, yy)
+            members.append((item, idx, oty, W, np.full(P.N, yy.mean())))
+        if members:
+            thetas_b, _, _, stats_b, _ = P.path_batch(
+                np.stack([mb[2] for mb in members]), LAMBDAS, np.stack([mb[4] for mb in members]),
+                np.full(len(members), float(LAMBDAS[0]) / 5.0), wdiag=np.stack([mb[3] for mb in members]))
+        for b, (item, idx, _, _, _) in enumerate(members):
+            thetas = list(thetas_b[b])
+            if item == 0:
+                fitted = [th[idx] for th in thetas]
+                ref = FTRUE if folds == 1 else y
+                model_mses = np.array([np.sum((ft - ref) ** 2) / ref.size for ft in fitted])
+                final = dict(thetas=thetas, fitted=fitted, stats=stats_b[b], model_mses=model_mses)
+                if folds == 1:
+                    mse_mat[:, 0] = np.array([np.sum((ft - y) ** 2) / y.size for ft in fitted])
+            else:
+                te = foldinds == item - 1
+                ti = P.nearest(AXES, data[te]) if AXES is not None else nearest_index(data[te], MESH)
+                yt = y[te]
+                mse_mat[:, item - 1] = np.array([np.sum((th[ti] - yt) ** 2) / yt.size for th in thetas])
+        concurrent = 1
+
     def do_item(item):
         nonlocal final
         if item == 0:
@@ -221,7 +260,7 @@ def mbs_impl(data, y, m, mesh=None, n_lambda=100, ftrue=None, lambdas=None, fold
         if verbose:
             print(f"[rank {rank}] work item {item} done")
 
-    mine = assign(n_items, world, rank)
+    mine = [] if batched else assign(n_items, world, rank)
     if concurrent > 1 and len(mine) > 1:
         from concurrent.futures import ThreadPoolExecutor
         with ThreadPoolExecutor(max_workers=min(concurrent, len(mine))) as ex:
