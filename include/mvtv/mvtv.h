@@ -220,9 +220,9 @@ mvtv_status mvtv_path(mvtv_problem* prob, const mvtv_admm_opts* opts, const doub
  * mvtv_path does, and the next lambda starts once every member has finished the current one. n_lambda = 1 is the
  * batched single fit. Honoured options: fixed_iters, tol, max_counter, pcg_rtol, pcg_max_iter, pcg_strict.
  * MVTV_BAD_ARG (before any launch) for: a mesh that is not admitted; a variant other than MVTV_VARIANT_RCPP; a
- * theta_solver other than AUTO or PCG; a non-NaN opts.sigma; nbatch < 1 or n_lambda < 1; a lambda < 0; a rho_init that is
+ * theta_solver other than AUTO or PCG (but see mvtv_problem_batch_cosine); a non-NaN opts.sigma; nbatch < 1 or n_lambda < 1; a lambda < 0; a rho_init that is
  * not positive and finite; a member whose W has a negative entry or no positive one. stats[b, l] holds that member's own iters, status, norms, eps, rho and
- * PCG counts (theta_solver = MVTV_SOLVER_PCG; seconds: the call's wall time). Returns MVTV_MAXITER when some (member,
+ * PCG counts (theta_solver = MVTV_SOLVER_PCG unless mvtv_problem_batch_cosine says otherwise; seconds: the call's wall time). Returns MVTV_MAXITER when some (member,
  * lambda) hit max_counter (the others are unaffected), MVTV_PCG_NOT_CONVERGED under pcg_strict likewise. */
 int32_t mvtv_problem_batch_ok(const mvtv_problem* prob);
 mvtv_status mvtv_path_batch(mvtv_problem* prob, const mvtv_admm_opts* opts, int32_t nbatch,
@@ -236,6 +236,24 @@ mvtv_status mvtv_path_batch(mvtv_problem* prob, const mvtv_admm_opts* opts, int3
                             double* u_out,            /* [nbatch x E], u after the last lambda in the problem's D row order, may be NULL */
                             double* rhos_out,         /* [nbatch x n_lambda], may be NULL */
                             mvtv_admm_stats* stats);  /* [nbatch x n_lambda], may be NULL */
+/* The batched fits' cosine theta-solve, opt-in per problem (mvtv_small_cos.hip): the cosine-transform solve inside the
+ * member's workgroup, dense transforms along every dimension but the longest and the factorised line solve along
+ * that one. mode 0 (the default): mvtv_path_batch as described above in every respect. mode 1: members with W = I
+ * (wdiag NULL, or a wdiag row of all ones) take the exact solve theta = (I + rho D^T D)^-1 b in place of the PCG loop
+ * (pcg_iters stays 0); the others run Jacobi-PCG as under mode 0. mode 2: the others run PCG preconditioned by
+ * S (mean(W) I + rho D^T D)^-1 S, the preconditioner and the scaling rule of MVTV_SOLVER_PCG_SPECTRAL evaluated per
+ * member with the current rho, under the stopping rule and counters of MVTV_SOLVER_PCG.
+ * With mode >= 1, opts.theta_solver means: AUTO as above, per member; PCG: Jacobi-PCG for every member; SPECTRAL:
+ * accepted when every member has W = I, else MVTV_BAD_ARG; PCG_SPECTRAL: needs mode 2 (else MVTV_BAD_ARG) and runs
+ * the preconditioned PCG for every member. stats.theta_solver reports what the member ran (MVTV_SOLVER_PCG,
+ * _SPECTRAL or _PCG_SPECTRAL). MVTV_BAD_ARG for a mode outside 0..2 and on a mesh mvtv_problem_batch_ok refuses. */
+mvtv_status mvtv_problem_batch_cosine(mvtv_problem* prob, int32_t mode);
+mvtv_status mvtv_problem_batch_cosine_get(const mvtv_problem* prob, int32_t* mode);
+/* x[b] = (shift[b] I + sigma[b] D^T D)^-1 f[b] for b < nbatch by that solve alone, one workgroup a member, whatever
+ * the problem's batch_cosine mode. sigma [nbatch] >= 0; shift [nbatch] > 0, or NULL: 1; f, x [nbatch x N], member-major
+ * (x may be f). MVTV_BAD_ARG on a mesh mvtv_problem_batch_ok refuses. */
+mvtv_status mvtv_solve_batch(mvtv_problem* prob, int32_t nbatch, const double* sigma, const double* shift,
+                             const double* f, double* x);
 /* fitted values O theta for n points given their mesh index (fill_output_mbs_one, rcpp…/solvers.cpp:73) */
 mvtv_status mvtv_fitted(mvtv_problem* prob, const int64_t* mesh_index, int64_t n, double* fitted);
 

@@ -96,6 +96,9 @@ SIGNATURES = {
     "mvtv_problem_batch_ok": (C.c_int32, [C.c_void_p]),
     "mvtv_path_batch": (C.c_int, [C.c_void_p, C.POINTER(AdmmOpts), C.c_int32, _dp, _dp, _dp, C.c_int32, _dp, _dp,
                                   _dp, _dp, _dp, C.POINTER(AdmmStats)]),
+    "mvtv_problem_batch_cosine": (C.c_int, [C.c_void_p, C.c_int32]),
+    "mvtv_problem_batch_cosine_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "mvtv_solve_batch": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, _dp, _dp]),
     "mvtv_fitted": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int64, _dp]),
     "mvtv_nearest": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int64, C.POINTER(C.c_int64)]),
     "mvtv_problem_set_scattered": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int64, _dp, C.POINTER(C.c_int64)]),
@@ -320,6 +323,27 @@ class Problem:
         if s not in (MVTV_OK, MVTV_MAXITER):
             _check(s)
         return thetas, u, rhos, [[sts[b * n + i].as_dict() for i in range(n)] for b in range(B)], s
+
+    def batch_cosine(self, mode):
+        """The batched fits' in-workgroup cosine theta-solve (mvtv_problem_batch_cosine): 0 off (the default), 1 the
+        exact solve for members with W = I, 2 also cosine-preconditioned PCG for the others."""
+        _check(lib().mvtv_problem_batch_cosine(self._h, int(mode)))
+
+    def batch_cosine_mode(self) -> int:
+        mode = C.c_int32()
+        _check(lib().mvtv_problem_batch_cosine_get(self._h, C.byref(mode)))
+        return mode.value
+
+    def solve_batch(self, b, sigma, shift=None):
+        """x[k] = (shift[k] I + sigma[k] D^T D)^-1 b[k] by the in-workgroup cosine solve alone, one workgroup a member
+        (mvtv_solve_batch). b [B x N]; sigma [B]; shift [B] or None (1). Returns x [B x N]."""
+        b = np.ascontiguousarray(np.asarray(b, dtype=np.float64).reshape(-1, self.N))
+        B = b.shape[0]
+        sg = _f64(sigma, B)
+        sh = None if shift is None else _f64(shift, B)
+        x = np.empty((B, self.N))
+        _check(lib().mvtv_solve_batch(self._h, B, _ptr(sg), _ptr(sh), _ptr(b), _ptr(x)))
+        return x
 
     def fitted(self, mesh_index):
         idx = np.ascontiguousarray(np.asarray(mesh_index, dtype=np.int64).ravel())

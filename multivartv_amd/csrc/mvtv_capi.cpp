@@ -180,6 +180,12 @@ void free_all(mvtv_problem* P) {
             (void)hipFree(*b);
             *b = nullptr;
         }
+    if (P->batch_buf) (void)hipFree(P->batch_buf);
+    P->batch_buf = nullptr;
+    P->batch_cap = 0;
+    if (P->cos.tab) (void)hipFree(const_cast<double*>(P->cos.tab));
+    if (P->cos.ab) (void)hipFree(const_cast<double*>(P->cos.ab));
+    P->cos = CosPlan{};
     if (P->st) (void)hipFree(P->st);
     if (P->ctl) (void)hipFree(P->ctl);
     if (P->host_ctl) (void)hipHostFree(P->host_ctl);
@@ -2011,9 +2017,152 @@ mvtv_status mvtv_path(mvtv_problem* P, const mvtv_admm_opts* opts, const double*
 
 int32_t mvtv_problem_batch_ok(const mvtv_problem* P) { return P && !P->slab && small_ok(P->g) ? 1 : 0; }
 
-// Many independent fits on the problem's mesh, each member's whole path in one workgroup (mvtv_small.hip). The lambda
-// loop is here: per lambda the launches of k_admm_small are enqueued two at a time and the device counter of members
-// that have not finished that lambda is read after each pair.
+} // extern "C"
+
+namespace {
+// The batched calls' device buffers: one allocation kept on the problem, grown when a call needs more, carved into
+// 256-byte aligned pieces in the order they are asked for.
+struct BatchArena {
+    mvtv_problem* P;
+    size_t need = 0;
+    std::vector<std::pair<void**, size_t>> parts;
+    template <class T>
+    void add(T** ptr, size_t n) {
+        parts.emplace_back(reinterpret_cast<void**>(ptr), need);
+        need += (std::max<size_t>(n, 1) * sizeof(T) + 255) & ~size_t(255);
+    }
+    mvtv_status commit() {
+        if (need > P->batch_cap) {
+            HIP_TRY(hipStreamSynchronize(P->stream));
+            if (P->batch_buf) (void)hipFree(P->batch_buf);
+            P->batch_buf = nullptr;
+            P->batch_cap = 0;
+            HIP_TRY(hipMalloc(&P->batch_buf, need));
+            P->batch_cap = need;
+        }
+        for (auto& pr : parts) *pr.first = static_cast<char*>(P->batch_buf) + pr.second;
+        return MVTV_OK;
+    }
+};
+
+// The in-workgroup cosine solve's tables (mvtv_small_cos.hip), built once per problem in long double and rounded:
+// per transformed dimension the orthonormal DCT-II matrix at the plan's pitch, per line of the line dimension
+// a = sum_{S without ld} cS[S] prod_{j in S} lam_j(k_j) and b = sum_{S with ld} cS[S] prod_{j in S, j != ld} lam_j(k_j),
+// lam_j(k) = 4 sin^2(pi k / 2 m_j), cS[S] the sum of w_k^2 over the blocks with S'(k) = S.
+mvtv_status cos_plan_setup(mvtv_problem* P) {
+    if (P->cos.ld >= 0) return MVTV_OK;
+    Geom g = P->g;
+    CosPlan cp;
+    if (!small_cos_shape(g, &cp)) return fail(MVTV_BAD_ARG, "the mesh does not admit the in-workgroup cosine solve");
+    const long double pi = 4.0L * std::atan(1.0L);
+    std::vector<double> tab(std::max<uint32_t>(cp.tab_words, 1), 0.0), ab(2 * size_t(cp.nlines));
+    std::vector<std::vector<long double>> lam(g.p);
+    for (int j = 0; j < g.p; ++j) {
+        const uint32_t m = g.m[j];
+        lam[j].resize(m);
+        for (uint32_t k = 0; k < m; ++k) {
+            const long double sn = std::sin(pi * (long double)k / (long double)(2 * m));
+            lam[j][k] = 4.0L * sn * sn;
+        }
+        if (j == cp.ld) continue;
+        const long double s0 = std::sqrt(1.0L / (long double)m), s1 = std::sqrt(2.0L / (long double)m);
+        for (uint32_t k = 0; k < m; ++k)
+            for (uint32_t n = 0; n < m; ++n) {
+                const uint32_t arg = uint32_t((uint64_t(2 * n + 1) * k) % (4 * m));   // the angle's period is 4m
+                tab[cp.toff[j] + size_t(k) * cp.pitch[j] + n] =
+                    double((k == 0 ? s0 : s1) * std::cos(pi * (long double)arg / (long double)(2 * m)));
+            }
+    }
+    long double cS[16] = {0};
+    for (int k = 0; k < g.nb; ++k) cS[P->sprime[k]] += (long double)g.w[k] * (long double)g.w[k];
+    const uint32_t lstride = g.stride[cp.ld], lm = g.m[cp.ld];
+    for (uint32_t line = 0; line < cp.nlines; ++line) {
+        const uint32_t hi = line / lstride, lo = line - hi * lstride;
+        uint32_t rest = lo + hi * lstride * lm, c[kMaxDims] = {0, 0, 0, 0};
+        for (int j = 0; j < g.p; ++j) {
+            c[j] = j < g.p - 1 ? rest % g.m[j] : rest;
+            rest /= g.m[j];
+        }
+        long double a = 0.0L, b = 0.0L;
+        for (int S = 1; S < (1 << g.p); ++S) {
+            long double prod = cS[S];
+            for (int j = 0; j < g.p; ++j)
+                if (((S >> j) & 1) && j != cp.ld) prod *= lam[j][c[j]];
+            if ((S >> cp.ld) & 1) b += prod;
+            else a += prod;
+        }
+        ab[line] = double(a);
+        ab[cp.nlines + line] = double(b);
+    }
+    double *d_tab = nullptr, *d_ab = nullptr;
+    MVTV_TRY(alloc(&d_tab, tab.size()));
+    if (alloc(&d_ab, ab.size()) != MVTV_OK) {
+        (void)hipFree(d_tab);
+        return MVTV_OUT_OF_MEMORY;
+    }
+    cp.tab = d_tab;
+    cp.ab = d_ab;
+    P->cos = cp;   // owned from here on (free_all)
+    HIP_TRY(hipMemcpy(d_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_ab, ab.data(), ab.size() * sizeof(double), hipMemcpyHostToDevice));
+    return MVTV_OK;
+}
+}  // namespace
+
+extern "C" {
+
+mvtv_status mvtv_problem_batch_cosine(mvtv_problem* P, int32_t mode) {
+    if (!P) return fail(MVTV_BAD_ARG, "null problem");
+    if (!mvtv_problem_batch_ok(P))
+        return fail(MVTV_BAD_ARG, "batch_cosine: batched fits need one GPU's whole mesh of at most 4096 nodes (p = 4: 1296)");
+    if (mode < 0 || mode > 2) return fail(MVTV_BAD_ARG, "batch_cosine: mode 0, 1 or 2");
+    DeviceGuard dg(P->device);
+    if (mode > 0) MVTV_TRY(cos_plan_setup(P));
+    P->batch_cos = mode;
+    return MVTV_OK;
+}
+
+mvtv_status mvtv_problem_batch_cosine_get(const mvtv_problem* P, int32_t* mode) {
+    if (!P || !mode) return fail(MVTV_BAD_ARG, "batch_cosine_get: null argument");
+    *mode = P->batch_cos;
+    return MVTV_OK;
+}
+
+mvtv_status mvtv_solve_batch(mvtv_problem* P, int32_t nbatch, const double* sigma, const double* shift, const double* f,
+                             double* x) {
+    if (!P || !sigma || !f || !x) return fail(MVTV_BAD_ARG, "null argument");
+    if (!mvtv_problem_batch_ok(P))
+        return fail(MVTV_BAD_ARG, "solve_batch: needs one GPU's whole mesh of at most 4096 nodes (p = 4: 1296)");
+    if (nbatch < 1) return fail(MVTV_BAD_ARG, "nbatch must be >= 1");
+    for (int32_t b = 0; b < nbatch; ++b) {
+        if (!(sigma[b] >= 0.0) || std::isinf(sigma[b])) return fail(MVTV_BAD_ARG, "sigma must be >= 0 and finite");
+        if (shift && (!(shift[b] > 0.0) || std::isinf(shift[b]))) return fail(MVTV_BAD_ARG, "shift must be positive and finite");
+    }
+    DeviceGuard dg(P->device);
+    MVTV_TRY(cos_plan_setup(P));
+    const size_t N = P->g.N, B = size_t(nbatch);
+    double *d_sigma = nullptr, *d_shift = nullptr, *d_x = nullptr;
+    BatchArena ar{P};
+    ar.add(&d_sigma, B);
+    ar.add(&d_shift, B);
+    ar.add(&d_x, B * N);
+    MVTV_TRY(ar.commit());
+    hipStream_t s = P->stream;
+    HIP_TRY(hipMemcpyAsync(d_sigma, sigma, B * sizeof(double), hipMemcpyHostToDevice, s));
+    if (shift) HIP_TRY(hipMemcpyAsync(d_shift, shift, B * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_x, f, B * N * sizeof(double), hipMemcpyHostToDevice, s));
+    Geom g = P->g;
+    g.eaos = 0;
+    HIP_TRY(launch_solve_cos(g, P->cos, s, nbatch, d_sigma, shift ? d_shift : nullptr, d_x, d_x));
+    HIP_TRY(hipMemcpyAsync(x, d_x, B * N * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return MVTV_OK;
+}
+
+// Many independent fits on the problem's mesh, each member's whole path in one workgroup (mvtv_small.hip,
+// mvtv_small_cos.hip). The lambda loop is here: per lambda the launches of the loop kernels (one per member kind
+// present) are enqueued two rounds at a time and the device counter of members that have not finished that lambda is
+// read after each pair.
 mvtv_status mvtv_path_batch(mvtv_problem* P, const mvtv_admm_opts* opts, int32_t nbatch, const double* oty,
                             const double* wdiag, const double* lambdas, int32_t n_lambda, const double* theta_init,
                             const double* rho_init, double* thetas_out, double* u_out, double* rhos_out,
@@ -2024,8 +2173,16 @@ mvtv_status mvtv_path_batch(mvtv_problem* P, const mvtv_admm_opts* opts, int32_t
     if (!mvtv_problem_batch_ok(P))
         return fail(MVTV_BAD_ARG, "batched fits need one GPU's whole mesh of at most 4096 nodes (p = 4: 1296)");
     if (o.variant != MVTV_VARIANT_RCPP) return fail(MVTV_BAD_ARG, "batched fits run variant B only");
-    if (o.theta_solver != MVTV_SOLVER_AUTO && o.theta_solver != MVTV_SOLVER_PCG)
-        return fail(MVTV_BAD_ARG, "batched fits solve for theta by PCG");
+    const int cosm = P->batch_cos;
+    if (cosm == 0) {
+        if (o.theta_solver != MVTV_SOLVER_AUTO && o.theta_solver != MVTV_SOLVER_PCG)
+            return fail(MVTV_BAD_ARG, "batched fits solve for theta by PCG");
+    } else {
+        if (o.theta_solver < MVTV_SOLVER_AUTO || o.theta_solver > MVTV_SOLVER_PCG_SPECTRAL)
+            return fail(MVTV_BAD_ARG, "unknown theta_solver");
+        if (o.theta_solver == MVTV_SOLVER_PCG_SPECTRAL && cosm < 2)
+            return fail(MVTV_BAD_ARG, "batched fits: PCG_SPECTRAL needs batch_cosine mode 2");
+    }
     if (!std::isnan(o.sigma)) return fail(MVTV_BAD_ARG, "batched fits take the matrix scalar rho (sigma must be NaN)");
     if (nbatch < 1 || n_lambda < 1) return fail(MVTV_BAD_ARG, "nbatch and n_lambda must be >= 1");
     const size_t N = P->g.N, nbN = size_t(P->g.nb) * N, B = size_t(nbatch), NL = size_t(n_lambda);
@@ -2033,42 +2190,68 @@ mvtv_status mvtv_path_batch(mvtv_problem* P, const mvtv_admm_opts* opts, int32_t
         if (!(lambdas[i] >= 0.0)) return fail(MVTV_BAD_ARG, "lambda must be >= 0");
     for (size_t b = 0; b < B; ++b)
         if (!(rho_init[b] > 0.0) || std::isinf(rho_init[b])) return fail(MVTV_BAD_ARG, "rho_init must be positive and finite");
+    // the validation scan of W also gives each member's kind (a row of all ones is W = I) and mean(W), std(W)
+    std::vector<int32_t> kind;
+    std::vector<double> wstat;
+    if (cosm > 0) {
+        kind.assign(B, SMALL_KIND_COS);
+        wstat.assign(2 * B, 0.0);
+        for (size_t b = 0; b < B; ++b) wstat[2 * b] = 1.0;
+    }
     if (wdiag)
         for (size_t b = 0; b < B; ++b) {
-            bool pos = false;
+            bool pos = false, ones = true;
+            double sum = 0.0, sum2 = 0.0;
             for (size_t i = 0; i < N; ++i) {
-                if (!(wdiag[b * N + i] >= 0.0)) return fail(MVTV_BAD_ARG, "W must be >= 0");
-                pos = pos || wdiag[b * N + i] > 0.0;
+                const double w = wdiag[b * N + i];
+                if (!(w >= 0.0)) return fail(MVTV_BAD_ARG, "W must be >= 0");
+                pos = pos || w > 0.0;
+                ones = ones && w == 1.0;
+                sum += w;
+                sum2 += w * w;
             }
             if (!pos) return fail(MVTV_BAD_ARG, "a member's W has no positive entry");
+            if (cosm > 0 && !ones) {
+                const double mean = sum / double(N);
+                kind[b] = SMALL_KIND_COS_PCG;
+                wstat[2 * b] = mean;
+                wstat[2 * b + 1] = std::sqrt(std::max(0.0, sum2 / double(N) - mean * mean));
+            }
         }
+    bool has[3] = {cosm == 0, false, false};
+    if (cosm > 0) {
+        for (size_t b = 0; b < B; ++b) {
+            int32_t& k = kind[b];
+            if (o.theta_solver == MVTV_SOLVER_SPECTRAL && k != SMALL_KIND_COS)
+                return fail(MVTV_BAD_ARG, "batched fits: SPECTRAL needs W = I for every member");
+            if (o.theta_solver == MVTV_SOLVER_PCG) k = SMALL_KIND_JACOBI;
+            else if (o.theta_solver == MVTV_SOLVER_PCG_SPECTRAL) k = SMALL_KIND_COS_PCG;
+            else if (k == SMALL_KIND_COS_PCG && cosm < 2) k = SMALL_KIND_JACOBI;
+            has[k] = true;
+        }
+        MVTV_TRY(cos_plan_setup(P));
+    }
     DeviceGuard dg(P->device);
-    // the call's own device buffers, released on every return path
-    struct Bufs {
-        std::vector<void*> v;
-        ~Bufs() {
-            for (void* p : v) (void)hipFree(p);
-        }
-    } bufs;
-    auto dev = [&](auto** ptr, size_t n) -> mvtv_status {
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(ptr), std::max<size_t>(n, 1) * sizeof(**ptr)));
-        bufs.v.push_back(*ptr);
-        return MVTV_OK;
-    };
     double *d_oty = nullptr, *d_w = nullptr, *d_lam = nullptr, *d_theta = nullptr, *d_z = nullptr, *d_gag = nullptr,
-           *d_thetas = nullptr;
+           *d_thetas = nullptr, *d_wstat = nullptr;
     SmallCtl *d_ctl = nullptr, *d_log = nullptr;
-    int32_t* d_rem = nullptr;
-    MVTV_TRY(dev(&d_oty, B * N));
-    if (wdiag) MVTV_TRY(dev(&d_w, B * N));
-    MVTV_TRY(dev(&d_lam, B * NL));
-    MVTV_TRY(dev(&d_theta, B * N));
-    MVTV_TRY(dev(&d_z, B * nbN));
-    MVTV_TRY(dev(&d_gag, B * 2 * N));
-    if (thetas_out) MVTV_TRY(dev(&d_thetas, B * NL * N));
-    MVTV_TRY(dev(&d_ctl, B));
-    MVTV_TRY(dev(&d_log, B * NL));
-    MVTV_TRY(dev(&d_rem, NL));
+    int32_t *d_rem = nullptr, *d_kind = nullptr;
+    BatchArena ar{P};
+    ar.add(&d_oty, B * N);
+    if (wdiag) ar.add(&d_w, B * N);
+    ar.add(&d_lam, B * NL);
+    ar.add(&d_theta, B * N);
+    ar.add(&d_z, B * nbN);
+    ar.add(&d_gag, B * 2 * N);
+    if (thetas_out) ar.add(&d_thetas, B * NL * N);
+    ar.add(&d_ctl, B);
+    ar.add(&d_log, B * NL);
+    ar.add(&d_rem, NL);
+    if (cosm > 0) {
+        ar.add(&d_kind, B);
+        ar.add(&d_wstat, 2 * B);
+    }
+    MVTV_TRY(ar.commit());
     std::vector<SmallCtl> ctl(B);
     for (size_t b = 0; b < B; ++b) {
         ctl[b] = SmallCtl{};
@@ -2085,12 +2268,17 @@ mvtv_status mvtv_path_batch(mvtv_problem* P, const mvtv_admm_opts* opts, int32_t
     HIP_TRY(hipMemsetAsync(d_z, 0, B * nbN * sizeof(double), s));
     HIP_TRY(hipMemcpyAsync(d_ctl, ctl.data(), B * sizeof(SmallCtl), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d_rem, rem.data(), NL * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (cosm > 0) {
+        HIP_TRY(hipMemcpyAsync(d_kind, kind.data(), B * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d_wstat, wstat.data(), 2 * B * sizeof(double), hipMemcpyHostToDevice, s));
+    }
 
     Geom g = P->g;
     g.eaos = 0;
     SmallArgs a{};
     a.oty = d_oty, a.wdiag = d_w, a.lambdas = d_lam, a.theta = d_theta, a.z = d_z, a.gag = d_gag;
     a.ctl = d_ctl, a.log = d_log, a.thetas_out = d_thetas, a.remaining = d_rem;
+    a.kind = d_kind, a.wstat = d_wstat;
     a.n_lambda = n_lambda;
     a.fixed_iters = o.fixed_iters;
     a.max_counter = variant_maxc(o);
@@ -2110,8 +2298,11 @@ mvtv_status mvtv_path_batch(mvtv_problem* P, const mvtv_admm_opts* opts, int32_t
         int32_t left = nbatch;
         for (int64_t done = 0; left > 0; done += 2) {
             if (done >= launch_cap) return fail(MVTV_HIP_ERROR, "batched fits: members unfinished after the iteration bound");
-            HIP_TRY(launch_admm_small(g, s, nbatch, a));
-            HIP_TRY(launch_admm_small(g, s, nbatch, a));
+            for (int rep = 0; rep < 2; ++rep) {
+                if (has[SMALL_KIND_JACOBI]) HIP_TRY(launch_admm_small(g, s, nbatch, a));
+                if (has[SMALL_KIND_COS]) HIP_TRY(launch_admm_cos(g, P->cos, s, nbatch, a, false));
+                if (has[SMALL_KIND_COS_PCG]) HIP_TRY(launch_admm_cos(g, P->cos, s, nbatch, a, true));
+            }
             HIP_TRY(hipMemcpyAsync(&left, d_rem + li, sizeof(int32_t), hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
         }
@@ -2165,7 +2356,9 @@ mvtv_status mvtv_path_batch(mvtv_problem* P, const mvtv_admm_opts* opts, int32_t
             S.pcg_iters_max = c.pcg_max;
             S.pcg_unconverged = c.pcg_unconv;
             S.seconds = seconds;
-            S.theta_solver = MVTV_SOLVER_PCG;
+            const int32_t k = cosm > 0 ? kind[i / NL] : int32_t(SMALL_KIND_JACOBI);
+            S.theta_solver = k == SMALL_KIND_COS ? MVTV_SOLVER_SPECTRAL
+                                                 : (k == SMALL_KIND_COS_PCG ? MVTV_SOLVER_PCG_SPECTRAL : MVTV_SOLVER_PCG);
             stats[i] = S;
         }
     }

@@ -53,6 +53,31 @@ __device__ __forceinline__ void block_reduce_store(double (&v)[NR], double* __re
     }
 }
 
+// The line solves' multipliers (mvtv_spectral.hip "Multipliers", mvtv_small_cos.hip): t_n = 1 - r^n from t = 1 - r
+// alone (t_{a+b} = t_a + t_b - t_a t_b: a few eps relative for any n), and r^n as the pair h + l with h = 1 - t
+// rounded and l = (1 - h) - t, exact where h >= 1/2.
+__device__ __forceinline__ double tpow(double t, uint32_t n) {   // 1 - r^n from t = 1 - r
+    double y = 0.0, x = t;
+    while (n) {
+        if (n & 1u) y = fma(-y, x, y + x);
+        x = fma(-x, x, x + x);
+        n >>= 1;
+    }
+    return y;
+}
+struct Mul2 {
+    double h, l;
+};
+__device__ __forceinline__ Mul2 mul2_from_t(double t) {
+    const double h = 1.0 - t;
+    return {h, h >= 0.5 ? (1.0 - h) - t : 0.0};
+}
+__device__ __forceinline__ double mul2_mac(Mul2 m, double acc, double f) { return fma(m.h, acc, fma(m.l, acc, f)); }
+__device__ __forceinline__ Mul2 mul2_mul(Mul2 a, Mul2 b) {
+    const double h = a.h * b.h;
+    return {h, fma(a.h, b.h, -h) + fma(a.h, b.l, a.l * b.h)};
+}
+
 // 3^p stencil coefficients of D^T D (mvtv_kernels.hip make_stencil), passed to kernels by value
 struct StencilK {
     double K[81];

@@ -506,8 +506,46 @@ struct SmallArgs {
     int32_t n_lambda, li, fixed_iters, max_counter, pcg_maxit, pcg_strict;
     double tol, rtol2, sqrtN, sqrtE;
     int32_t sp[kMaxBlocks];  // S' mask per block
+    // mvtv_problem_batch_cosine: the kernel each member runs (SMALL_KIND_*); nullptr: k_admm_small runs every member
+    const int32_t* kind;     // [nbatch]
+    const double* wstat;     // [nbatch][2]: mean(W), std(W) of the members of kind SMALL_KIND_COS_PCG
 };
+enum SmallKind { SMALL_KIND_JACOBI = 0, SMALL_KIND_COS = 1, SMALL_KIND_COS_PCG = 2 };
 hipError_t launch_admm_small(const Geom& g, hipStream_t s, int nbatch, const SmallArgs& a);
+
+// ---- the in-workgroup cosine solve of the batched fits (mvtv_small_cos.hip) ----------------------------------
+// (shift I + sigma D^T D) x = f on a mesh small_ok admits, for a vector in LDS: dense cosine transforms from tables
+// along every dimension but the longest (<= 64 points each, since (second longest)^2 <= N <= 4096), the factorised
+// line solve along the longest (ties: the last of them). k_solve_cos<P, NT> runs it alone (mvtv_solve_batch),
+// k_admm_cos<P, NT, ZLDS, PC> inside the loop of k_admm_small: PC = false the exact theta-solve of a W = I member,
+// PC = true PCG on W + rho D^T D preconditioned by S A0^-1 S, A0 = mean(W) I + rho D^T D, as pcgs_solve.
+// The tables take up to 64 * 65 words of LDS beside sv, so these kernels keep z in LDS up to fewer edge words:
+constexpr uint32_t kSmallCosZLds = 11264;   // edge words nb * N kept in LDS by k_admm_cos (88 KiB)
+constexpr uint32_t kSmallCosMaxT = 64;      // the longest transformed dimension
+inline bool small_cos_zlds(int nb, uint32_t N) { return uint64_t(nb) * N <= kSmallCosZLds; }
+struct CosPlan {
+    int32_t ld = -1;                 // the line dimension; -1: no plan
+    int32_t tpl = 0, sl = 0;         // threads a line gets (a power of two, nlines * tpl <= NT), rows a segment
+    uint32_t nlines = 0;             // N / m[ld]; line l = lo + hi stride[ld] starts at node lo + hi stride[ld] m[ld]
+    uint32_t tab_words = 0;          // the dense tables' words
+    uint32_t toff[kMaxDims] = {0, 0, 0, 0};    // per transformed dimension j: its table's offset in tab,
+    uint32_t pitch[kMaxDims] = {0, 0, 0, 0};   // its row pitch m_j | 1: C_j[k][n] at toff + k pitch + n
+    const double* tab = nullptr;     // device: orthonormal DCT-II matrices s_k cos(pi (2n + 1) k / 2 m_j)
+    const double* ab = nullptr;      // device: a[nlines], b[nlines]: a line's c0 = shift + sigma a, c1 = sigma b
+};
+// the plan's shape for mesh g (everything but the device tables); false where the mesh is not admitted
+bool small_cos_shape(const Geom& g, CosPlan* cp);
+// dynamic LDS of the two kernels: sv [N], the reduction buffers [2][NT / 64][3], the scan's [3][NT / 64], the tables,
+// and for the loop z [nb][N] when small_cos_zlds
+inline size_t small_cos_lds_bytes(const Geom& g, const CosPlan& cp, bool loop) {
+    return (size_t(g.N) + 9u * size_t(small_nt(g.N) / 64) + cp.tab_words +
+            (loop && small_cos_zlds(g.nb, g.N) ? size_t(g.nb) * g.N : 0u)) * sizeof(double);
+}
+// the members of a.kind == (pc ? SMALL_KIND_COS_PCG : SMALL_KIND_COS)
+hipError_t launch_admm_cos(const Geom& g, const CosPlan& cp, hipStream_t s, int nbatch, const SmallArgs& a, bool pc);
+// x[b] = (shift[b] I + sigma[b] D^T D)^-1 f[b], b < nbatch; shift = nullptr: 1
+hipError_t launch_solve_cos(const Geom& g, const CosPlan& cp, hipStream_t s, int nbatch, const double* sigma,
+                            const double* shift, const double* f, double* x);
 
 // scattered-data setup (mvtv_scatter.hip)
 // axes_host_span[j] = axis_j[last] - axis_j[0] (host values; only the first guess of the bracket)

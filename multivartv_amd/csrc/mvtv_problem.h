@@ -119,6 +119,13 @@ struct mvtv_problem {
     };
     std::vector<LoopGraph> graphs;
 
+    // batched small-mesh fits (mvtv_path_batch, mvtv_solve_batch)
+    int batch_cos = 0;            // mvtv_problem_batch_cosine: 0 Jacobi-PCG for all, 1 exact cosine solve for W = I
+                                  // members, 2 also cosine-preconditioned PCG for the others
+    CosPlan cos;                  // the in-workgroup cosine solve's plan and device tables (cos.ld < 0: not built)
+    void* batch_buf = nullptr;    // the batched calls' device buffers, kept between calls and grown on demand
+    size_t batch_cap = 0;
+
     // slab decomposition (mvtv_problem_create_slab): this problem holds planes [zb, ze) of dim p-1
     // of a mesh with m_global planes, plus ghost planes below / above
     bool slab = false;

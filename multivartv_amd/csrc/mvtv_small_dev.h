@@ -1,29 +1,13 @@
-// mvtv_small.hip — batched small-mesh fits: the whole variant-B ADMM loop of one batch member in one workgroup.
-//
-// k_admm_small<P, NT, ZLDS>: grid = batch members, NT threads each, no workgroup reads another member's data and none
-// waits for another. Per ADMM iteration (rcpp-code/MultivarTV/src/solvers.cpp:110-133):
-//   b = O^T y + rho (D^T alpha + c D^T u)                       from the node-owned D^T alpha, D^T u of the last gather
-//   theta = (W + rho D^T D)^-1 b                                Jacobi-PCG, warm-started, the rule of MVTV_SOLVER_PCG
-//   z = D theta - u_old, alpha = soft(z, lambda / rho), r, u    one pass over the member's edge state
-//   D^T alpha, D^T u, s = rho D^T (u - u_old)                   one gather per node
-//   the five norms, eps, adapt_step, the stopping test          every thread, from the same reduced numbers
-// State. A thread owns the nodes tid + q NT (q < KPT) and keeps their theta, PCG residual and direction and W in
-// registers; their D^T alpha and D^T u, read and written once an ADMM iteration by the owner alone, stay in the
-// member's HBM scratch (where an unfinished member needs them anyway). What neighbours read goes through LDS: one
-// vector `sv` [N] (theta for D theta and the first residual, the PCG direction inside the solve) and the edge state
-// z [nb][N] in the padded layout of mvtv_kernels.hip (u = -c clamp(z, t_z), alpha = z - clamp(z, t_z)); z stays in the
-// member's HBM scratch when nb N exceeds kSmallZLds. Reductions: a shuffle tree in each wave, then a fixed tree over
-// the waves' sums in every lane, so each thread holds the same bits and takes the same branches. The two reduction
-// buffers alternate: a buffer is rewritten only after the barrier of the next reduction, which every thread reaches
-// after its reads of the first.
-// A launch runs at most kSmallChunk iterations; theta, z, D^T alpha, D^T u and SmallCtl round-trip through HBM.
-// mvtv_small_dev.h holds the same loop as a device function over its theta-solve for k_admm_cos (mvtv_small_cos.hip);
-// a change to the loop here belongs there too.
+// mvtv_small_dev.h — the batched small-mesh ADMM loop of one member in one workgroup, as a device function over its
+// theta-solve, for k_admm_cos (mvtv_small_cos.hip). The loop, its state and its reductions are those of k_admm_small
+// and are described at the top of mvtv_small.hip, which keeps its own copy of the loop in the kernel body: built
+// from this function k_admm_small came out 10 VGPRs heavier, and at p = 4 with the 81 stencil coefficients copied to
+// scratch (656 B a lane), so the two are kept in step by hand (the helpers here are mvtv_small.hip's, verbatim).
+#pragma once
 #include "mvtv_device.h"
 
 namespace mvtv {
-
-namespace {
+namespace small {
 
 // a value every lane holds, moved to scalar registers (branches on it are wave-uniform for the compiler too)
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
@@ -39,6 +23,12 @@ __device__ __forceinline__ double uni(double v) {
 __device__ __forceinline__ uint32_t opaque(uint32_t v) {
     asm volatile("" : "+v"(v));
     return v;
+}
+
+// nodes a thread: 4096 / 1024, 1024 / 256, 256 / 64; 1296 / 1024
+template <int P, int NT>
+constexpr int kpt() {
+    return (P == 4 && NT == 1024) ? 2 : 4;
 }
 
 // (D^T D x)_i as stencil_DtD, for p >= 3 one hyperplane of the last dimension at a time: 9 or 27 loads in flight
@@ -107,24 +97,37 @@ __device__ __forceinline__ void wg_sum(double (&v)[NR], double* __restrict__ sm,
     }
 }
 
-}  // namespace
+// What a theta-solve sees of its member: the neighbour-read vector sv [N] (holding theta on entry, and again on
+// return), the reduction buffers, the member's right-hand-side terms. A solve is called by every thread with
+// (ctx, c, rho, x, wv): the thread's nodes' theta in x (in and out) and W in wv; it adds its counts to c and returns
+// true when the member must stop (c.status set).
+struct SolveCtx {
+    double* sv;
+    double* sm;
+    const double* oty;
+    const double* gg;   // [2][N]: D^T alpha, D^T u
+    uint32_t N, tid, mb;
+};
 
-template <int P, int NT, bool ZLDS>
-__global__ __launch_bounds__(NT) void k_admm_small(Geom g, StencilK sk, SmallArgs a) {
-    constexpr int KPT = (P == 4 && NT == 1024) ? 2 : 4;   // nodes a thread: 4096 / 1024, 1024 / 256, 256 / 64; 1296 / 1024
+// the right-hand side b = O^T y + rho (D^T alpha + c D^T u) at node i
+__device__ __forceinline__ double small_rhs(const SolveCtx& s, const SmallCtl& c, double rho, uint32_t i) {
+    return fma(rho * c.c, s.gg[s.N + i], fma(rho, s.gg[i], s.oty[i]));
+}
+
+// The loop of one member. KIND: the member kind this kernel runs (SmallArgs::kind; every member when that is null).
+// sv [N], sm [2][NT / 64][3] and zl [nb][N] (ZLDS) are the workgroup's LDS.
+template <int P, int NT, bool ZLDS, int KIND, class Solve>
+__device__ __forceinline__ void admm_small_loop(const Geom& g, const double* __restrict__ K, const SmallArgs& a, double* const sv,
+                                                double* const sm, double* const zl, const Solve& solve) {
+    constexpr int KPT = kpt<P, NT>();
     constexpr int NC = 1 << P;
-    constexpr int NW = NT / 64;
-    extern __shared__ double lds[];
     const uint32_t mb = blockIdx.x, tid = threadIdx.x, N = g.N;
     const int nb = g.nb;
-    if (a.kind && a.kind[mb] != SMALL_KIND_JACOBI) return;   // a member of k_admm_cos (mvtv_problem_batch_cosine)
+    if (a.kind && a.kind[mb] != KIND) return;   // another kernel's member
     SmallCtl* const cp = a.ctl + mb;
     SmallCtl c = *cp;
     if (c.cur_l == a.li && c.done) return;   // finished members return at once
 
-    double* const sv = lds;
-    double* const sm = sv + N;
-    double* const zl = sm + 2 * NW * 3;
     const double* const oty = a.oty + size_t(mb) * N;
     const double* const wd = a.wdiag ? a.wdiag + size_t(mb) * N : nullptr;
     double* const theta = a.theta + size_t(mb) * N;
@@ -204,13 +207,14 @@ __global__ __launch_bounds__(NT) void k_admm_small(Geom g, StencilK sk, SmallArg
                 decode<P>(g, i, cc);
                 double unused, gu0;
                 gather(i, cc, c.t_z, unused, gu0);
-                gg[i] = stencil_small<P>(g, sv, i, cc, sk.K);   // D^T alpha_0 = D^T D theta_0
+                gg[i] = stencil_small<P>(g, sv, i, cc, K);   // D^T alpha_0 = D^T D theta_0
                 gg[N + i] = gu0;
             }
         }
     }
 
     int flip = 0, nl = 0;
+    const SolveCtx sctx{sv, sm, oty, gg, N, tid, mb};
     for (;;) {
         // ---- the loop condition, at the top as in the reference (:110) ----
         const bool stop = a.fixed_iters > 0 ? c.it >= a.fixed_iters : !(c.dual > c.eps_d || c.primal > c.eps_p);
@@ -221,92 +225,12 @@ __global__ __launch_bounds__(NT) void k_admm_small(Geom g, StencilK sk, SmallArg
         if (nl == kSmallChunk) break;
         ++nl;
         const double rho = c.rho;
-        // ---- theta-solve: Jacobi-PCG on W + rho D^T D from the previous theta (sv holds theta) ----
-        double r[KPT], pd[KPT], zz[KPT];
-        double r3[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-        for (int q = 0; q < KPT; ++q) {
-            const uint32_t i = opaque(tid + q * NT);
-            r[q] = pd[q] = zz[q] = 0.0;
-            if (i < N) {
-                uint32_t cc[kMaxDims];
-                decode<P>(g, i, cc);
-                const double b = fma(rho * c.c, gg[N + i], fma(rho, gg[i], oty[i]));
-                const double ax = fma(rho, stencil_small<P>(g, sv, i, cc, sk.K), wv[q] * x[q]);
-                r[q] = b - ax;
-                pd[q] = r[q] / fma(rho, jacobi_diag<P, W_NONE>(g, 1.0, nullptr, i, cc), wv[q]);
-                r3[PR_B2] = fma(b, b, r3[PR_B2]);
-                r3[PR_RZ] = fma(r[q], pd[q], r3[PR_RZ]);
-                r3[PR_R2] = fma(r[q], r[q], r3[PR_R2]);
-            }
-        }
-        wg_sum<3, NT>(r3, sm, flip);
-        const double b2 = r3[PR_B2];
-        double gamma = r3[PR_RZ], r2 = r3[PR_R2];
-        int pit = 0;
-        bool pdone = (r2 <= a.rtol2 * b2) || a.pcg_maxit <= 0;
-        while (!uni(int(pdone))) {   // at most pcg_maxit passes
-#pragma unroll
-            for (int q = 0; q < KPT; ++q) {
-                const uint32_t i = opaque(tid + q * NT);
-                if (i < N) sv[i] = pd[q];
-            }
-            __syncthreads();
-            double qv[KPT];
-            double r1[1] = {0.0};
-#pragma unroll
-            for (int q = 0; q < KPT; ++q) {
-                const uint32_t i = opaque(tid + q * NT);
-                qv[q] = 0.0;
-                if (i < N) {
-                    uint32_t cc[kMaxDims];
-                    decode<P>(g, i, cc);
-                    qv[q] = fma(rho, stencil_small<P>(g, sv, i, cc, sk.K), wv[q] * pd[q]);
-                    r1[0] = fma(pd[q], qv[q], r1[0]);
-                }
-            }
-            wg_sum<1, NT>(r1, sm, flip);
-            const double alpha = gamma / r1[0];
-            double r2v[2] = {0.0, 0.0};
-#pragma unroll
-            for (int q = 0; q < KPT; ++q) {
-                const uint32_t i = opaque(tid + q * NT);
-                if (i < N) {
-                    uint32_t cc[kMaxDims];
-                    decode<P>(g, i, cc);
-                    x[q] = fma(alpha, pd[q], x[q]);
-                    r[q] = fma(-alpha, qv[q], r[q]);
-                    zz[q] = r[q] / fma(rho, jacobi_diag<P, W_NONE>(g, 1.0, nullptr, i, cc), wv[q]);
-                    r2v[0] = fma(r[q], zz[q], r2v[0]);
-                    r2v[1] = fma(r[q], r[q], r2v[1]);
-                }
-            }
-            wg_sum<2, NT>(r2v, sm, flip);
-            const double beta = r2v[0] / gamma;
-            gamma = r2v[0];
-            r2 = r2v[1];
-            ++pit;
-            pdone = (r2 <= a.rtol2 * b2) || pit >= a.pcg_maxit;
-#pragma unroll
-            for (int q = 0; q < KPT; ++q) pd[q] = fma(beta, pd[q], zz[q]);
-        }
-        c.pcg_iters += pit;
-        c.pcg_max = pit > c.pcg_max ? pit : c.pcg_max;
-        if (pit >= a.pcg_maxit && !(r2 <= a.rtol2 * b2)) {
-            c.pcg_unconv += 1;
-            if (a.pcg_strict) {
-                c.status = 7;   // MVTV_PCG_NOT_CONVERGED
-                c.done = 1;
-                break;
-            }
+        // ---- theta-solve: leaves theta in x and, behind a barrier, in sv ----
+        if (solve(g, K, a, sctx, flip, c, rho, x, wv)) {
+            c.done = 1;
+            break;
         }
         // ---- z-update, dual update (:114-116) ----
-#pragma unroll
-        for (int q = 0; q < KPT; ++q) {
-            const uint32_t i = opaque(tid + q * NT);
-            if (i < N) sv[i] = x[q];
-        }
-        __syncthreads();
         const double t_new = rho != 0.0 ? c.lambda / rho : INFINITY;
         double e3[3] = {0.0, 0.0, 0.0};
 #pragma unroll
@@ -384,6 +308,12 @@ __global__ __launch_bounds__(NT) void k_admm_small(Geom g, StencilK sk, SmallArg
         c.t_z = t_new;
         c.c = c_next;
         c.rho = rho_next;
+        if constexpr (Solve::kScalarCtl) {
+            // the control block's doubles, computed in vector registers (there is no scalar fp64), back into scalar
+            // ones: 16 registers a lane that a solve with more state of its own needs
+            c.dual = uni(c.dual), c.primal = uni(c.primal), c.eps_d = uni(c.eps_d), c.eps_p = uni(c.eps_p);
+            c.t_z = uni(c.t_z), c.c = uni(c.c), c.rho = uni(c.rho);
+        }
         if (a.fixed_iters <= 0 && c.counter > a.max_counter) {
             c.status = 1;   // MVTV_MAXITER
             c.done = 1;
@@ -413,43 +343,5 @@ __global__ __launch_bounds__(NT) void k_admm_small(Geom g, StencilK sk, SmallArg
     }
 }
 
-hipError_t launch_admm_small(const Geom& g, hipStream_t s, int nbatch, const SmallArgs& a) {
-    if (!small_ok(g) || nbatch < 1) return hipErrorInvalidValue;
-    const StencilK sk = make_stencil(g);
-    const int nt = small_nt(g.N);
-    const bool zlds = small_zlds(g.nb, g.N);
-    const size_t smem = small_lds_bytes(g);
-    auto go = [&](auto kern) {
-        if (smem > 65536) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, int(smem));
-            if (e != hipSuccess) return e;
-        }
-        klaunch(kern, dim3(uint32_t(nbatch)), dim3(uint32_t(nt)), uint32_t(smem), s, g, sk, a);
-        return hipGetLastError();
-    };
-    // Every (P, NT, ZLDS) the admission and the two rules can reach (nb <= 1, 3, 7, 15 for p = 1..4): z leaves LDS
-    // at p = 3 for N > 2048 (2389 with six blocks) and at p = 4 for nb N > 14336, which is N > 955 with fifteen blocks
-    // (so also at NT = 256) and every N > 1024. A combination outside the list is refused, never run with the other
-    // kernel's LDS size.
-    const int key = g.p * 10000 + nt * 2 + (zlds ? 1 : 0);
-    switch (key) {
-        case 10000 + 64 * 2 + 1: return go(k_admm_small<1, 64, true>);
-        case 10000 + 256 * 2 + 1: return go(k_admm_small<1, 256, true>);
-        case 10000 + 1024 * 2 + 1: return go(k_admm_small<1, 1024, true>);
-        case 20000 + 64 * 2 + 1: return go(k_admm_small<2, 64, true>);
-        case 20000 + 256 * 2 + 1: return go(k_admm_small<2, 256, true>);
-        case 20000 + 1024 * 2 + 1: return go(k_admm_small<2, 1024, true>);
-        case 30000 + 64 * 2 + 1: return go(k_admm_small<3, 64, true>);
-        case 30000 + 256 * 2 + 1: return go(k_admm_small<3, 256, true>);
-        case 30000 + 1024 * 2 + 1: return go(k_admm_small<3, 1024, true>);
-        case 30000 + 1024 * 2 + 0: return go(k_admm_small<3, 1024, false>);
-        case 40000 + 64 * 2 + 1: return go(k_admm_small<4, 64, true>);
-        case 40000 + 256 * 2 + 1: return go(k_admm_small<4, 256, true>);
-        case 40000 + 256 * 2 + 0: return go(k_admm_small<4, 256, false>);
-        case 40000 + 1024 * 2 + 0: return go(k_admm_small<4, 1024, false>);
-        default: return hipErrorInvalidValue;
-    }
-}
-
+}  // namespace small
 }  // namespace mvtv

@@ -2518,27 +2518,7 @@ namespace trib {
 constexpr int SMAX = 32;
 }
 
-__device__ __forceinline__ double tpow(double t, uint32_t n) {   // 1 - r^n from t = 1 - r
-    double y = 0.0, x = t;
-    while (n) {
-        if (n & 1u) y = fma(-y, x, y + x);
-        x = fma(-x, x, x + x);
-        n >>= 1;
-    }
-    return y;
-}
-struct Mul2 {
-    double h, l;
-};
-__device__ __forceinline__ Mul2 mul2_from_t(double t) {
-    const double h = 1.0 - t;
-    return {h, h >= 0.5 ? (1.0 - h) - t : 0.0};
-}
-__device__ __forceinline__ double mul2_mac(Mul2 m, double acc, double f) { return fma(m.h, acc, fma(m.l, acc, f)); }
-__device__ __forceinline__ Mul2 mul2_mul(Mul2 a, Mul2 b) {
-    const double h = a.h * b.h;
-    return {h, fma(a.h, b.h, -h) + fma(a.h, b.l, a.l * b.h)};
-}
+// tpow, Mul2 and its helpers: mvtv_device.h (shared with mvtv_small_cos.hip)
 
 template <int PHASE, int SMAX, int TQ, int NS>
 __global__ __launch_bounds__((TQ * NS)) void k_trib(const SpecArgs a, int sl, uint32_t nblk, uint32_t ntile,

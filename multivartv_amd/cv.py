@@ -136,7 +136,7 @@ def assign(n_items: int, world: int, rank: int):
 
 
 def mbs_impl(data, y, m, mesh=None, n_lambda=100, ftrue=None, lambdas=None, folds=1, verbose=False, seed=0,
-             device=None, group=None, _runner=None, concurrent=1, batched=False):
+             device=None, group=None, _runner=None, concurrent=1, batched=False, batch_cosine=0):
     """rcpp…/solvers.cpp:305-376. Returns the reference's result list as a dict (rank 0; other
     ranks return only 'cv.mses' and 'lambda_minmse_ind').
 
@@ -149,7 +149,9 @@ def mbs_impl(data, y, m, mesh=None, n_lambda=100, ftrue=None, lambdas=None, fold
     ``batched``: this rank's work items (the final path and its folds) run as one ``Problem.path_batch`` call, each
     item a batch member with its own O^T y, W, theta_0 = mean of its y and rho_0 = lambda_0 / 5, its whole path run by
     one workgroup. Everything after the paths is unchanged. ValueError when the mesh is not admitted
-    (``Problem.batch_ok``) or ``_runner`` is given; ``concurrent`` is ignored.
+    (``Problem.batch_ok``) or ``_runner`` is given; ``concurrent`` is ignored. ``batch_cosine`` (0, 1 or 2) is passed to
+    ``Problem.batch_cosine`` before that call: the in-workgroup cosine theta-solve for W = I members (1) and as the
+    preconditioner of the others' PCG (2); 0, the default, leaves the Jacobi-PCG path as it is.
     """
     data = np.asarray(data, dtype=np.float64)
     if data.ndim == 1:
@@ -229,6 +231,8 @@ def mbs_impl(data, y, m, mesh=None, n_lambda=100, ftrue=None, lambdas=None, fold
             idx = P.nearest(AXES, x) if AXES is not None else nearest_index(x, MESH)
             W, oty = interp_weights(idx, P.N, yy)
             members.append((item, idx, oty, W, np.full(P.N, yy.mean())))
+        if batch_cosine:
+            P.batch_cosine(batch_cosine)
         if members:
             thetas_b, _, _, stats_b, _ = P.path_batch(
                 np.stack([mb[2] for mb in members]), LAMBDAS, np.stack([mb[4] for mb in members]),

@@ -11,9 +11,14 @@ of repeat 1, ..., so a drift of the box hits every leg alike): unbatched, concur
 Problem.path_batch call over the same six paths; the unbatched legs' own counts differ from it by a few iterations
 where their theta-solve stops elsewhere (pcg_rtol 1e-10, spectral preconditioner).
 
+The legs batched_cos1 / batched_cos2 are batched=True with batch_cosine=1 / 2 (the in-workgroup cosine theta-solve,
+mvtv_problem_batch_cosine); each batched leg's line carries its own mean PCG iterations per theta-solve.
+
 sweep: nbatch in --nbatch independent fits at one lambda (own data per member, cold start) through one
 Problem.path_batch call, against the same fits through Problem.admm one after another (the parent path; at most
 --seq-cap of them are run and the per-fit time is reported, so `seq_seconds` of a larger nbatch is that times nbatch).
+--cos-modes 0 1 2 runs each path_batch call once per batch_cosine mode, interleaved (one line each, `cos_mode`);
+--identity puts the data on the mesh nodes (W = I), the members mode 1's exact solve takes.
 """
 import argparse
 import json
@@ -63,13 +68,23 @@ def run_cv(a):
     _, _, _, stats, _ = P.path_batch(np.stack([q[0] for q in mem]), lams, np.stack([np.full(N, q[2]) for q in mem]),
                                      np.full(len(mem), lams[0] / 5.0), wdiag=np.stack([q[1] for q in mem]),
                                      want_thetas=False)
-    P.close()
     iters = sum(s["iters"] for row in stats for s in row)
     pcg = sum(s["pcg_iters"] for row in stats for s in row)
     base = dict(mode="cv", m=m, n=a.n, folds=a.folds, n_lambda=a.n_lambda, admm_iters=iters,
                 pcg_per_solve=pcg / max(iters, 1), maxiter_hits=sum(s["status"] == 1 for row in stats for s in row))
-    legs = {"unbatched": {}, "concurrent4": dict(concurrent=4), "batched": dict(batched=True)}
+    legs = {"unbatched": {}, "concurrent4": dict(concurrent=4), "batched": dict(batched=True),
+            "batched_cos1": dict(batched=True, batch_cosine=1), "batched_cos2": dict(batched=True, batch_cosine=2)}
     legs = {k: v for k, v in legs.items() if k in a.legs}
+    leg_pcg = {}
+    for leg, kw in legs.items():   # the cosine legs' own counts, untimed
+        if kw.get("batch_cosine"):
+            P.batch_cosine(kw["batch_cosine"])
+            _, _, _, st, _ = P.path_batch(np.stack([q[0] for q in mem]), lams, np.stack([np.full(N, q[2]) for q in mem]),
+                                          np.full(len(mem), lams[0] / 5.0), wdiag=np.stack([q[1] for q in mem]),
+                                          want_thetas=False)
+            leg_pcg[leg] = dict(admm_iters=sum(s["iters"] for row in st for s in row),
+                                pcg_per_solve=sum(s["pcg_iters"] for row in st for s in row) / max(iters, 1))
+    P.close()
     for leg, kw in legs.items():   # warm-up: kernels loaded, allocator warm
         cv.mbs_impl(x, y, m, lambdas=lams[:3], folds=a.folds, group=False, **kw)
     for rep in range(a.repeats):
@@ -77,7 +92,7 @@ def run_cv(a):
             t0 = time.perf_counter()
             out = cv.mbs_impl(x, y, m, lambdas=lams, folds=a.folds, group=False, **kw)
             dt = time.perf_counter() - t0
-            print(json.dumps(dict(base, leg=leg, rep=rep, seconds=dt, its_per_s=iters / dt,
+            print(json.dumps(dict(base, **leg_pcg.get(leg, {}), leg=leg, rep=rep, seconds=dt, its_per_s=iters / dt,
                                   best=out["lambda_minmse_ind"])), flush=True)
 
 
@@ -93,6 +108,10 @@ def run_sweep(a):
     mem = []
     for b in range(nmax):   # the same points, own responses per member
         rng = np.random.default_rng(1000 + b)
+        if a.identity:   # the data on the mesh nodes: W = I
+            y = np.where(np.all(mesh > 0.6, axis=1), 1.0, 0.0) + 0.3 * rng.standard_normal(N)
+            mem.append((y, np.ones(N), float(y.mean())))
+            continue
         y = np.where(np.all(x0 > 0.6, axis=1), 1.0, 0.0) + 0.3 * rng.standard_normal(a.n)
         W, oty = interp_weights(P.nearest(axes, x0), N, y)
         mem.append((oty, W, float(y.mean())))
@@ -100,7 +119,9 @@ def run_sweep(a):
     W = np.stack([q[1] for q in mem])
     th0 = np.stack([np.full(N, q[2]) for q in mem])
     rho0 = np.full(nmax, a.lam / 5.0)
-    P.path_batch(oty[:2], [a.lam], th0[:2], rho0[:2], wdiag=W[:2], want_thetas=False)   # warm-up
+    for cm in a.cos_modes:   # warm-up
+        P.batch_cosine(cm)
+        P.path_batch(oty[:2], [a.lam], th0[:2], rho0[:2], wdiag=W[:2], want_thetas=False)
     P.set_data(oty[0], W[0])
     P.admm(a.lam, th0[0], rho=a.lam / 5.0, return_u=False)
     for rep in range(a.repeats):
@@ -112,15 +133,18 @@ def run_sweep(a):
             seq_iters += P.admm(a.lam, th0[b], rho=a.lam / 5.0, return_u=False)[3]["iters"]
         per_fit = (time.perf_counter() - t0) / nseq
         for nb in a.nbatch:
-            t0 = time.perf_counter()
-            _, _, _, stats, _ = P.path_batch(oty[:nb], [a.lam], th0[:nb], rho0[:nb], wdiag=W[:nb], want_thetas=True)
-            dt = time.perf_counter() - t0
-            iters = sum(s[0]["iters"] for s in stats)
-            pcg = sum(s[0]["pcg_iters"] for s in stats)
-            print(json.dumps(dict(mode="sweep", m=m, n=a.n, lam=a.lam, rep=rep, nbatch=nb, seconds=dt, admm_iters=iters,
-                                  its_per_s=iters / dt, pcg_per_solve=pcg / max(iters, 1), seq_fits_timed=nseq,
-                                  seq_seconds_per_fit=per_fit, seq_its_per_s=seq_iters / (per_fit * nseq),
-                                  speedup=per_fit * nb / dt)), flush=True)
+            for cm in a.cos_modes:
+                P.batch_cosine(cm)
+                t0 = time.perf_counter()
+                _, _, _, stats, _ = P.path_batch(oty[:nb], [a.lam], th0[:nb], rho0[:nb], wdiag=W[:nb], want_thetas=True)
+                dt = time.perf_counter() - t0
+                iters = sum(s[0]["iters"] for s in stats)
+                pcg = sum(s[0]["pcg_iters"] for s in stats)
+                print(json.dumps(dict(mode="sweep", m=m, n=a.n, lam=a.lam, rep=rep, nbatch=nb, cos_mode=cm,
+                                      identity=bool(a.identity), seconds=dt, admm_iters=iters, its_per_s=iters / dt,
+                                      pcg_per_solve=pcg / max(iters, 1), seq_fits_timed=nseq,
+                                      seq_seconds_per_fit=per_fit, seq_its_per_s=seq_iters / (per_fit * nseq),
+                                      speedup=per_fit * nb / dt)), flush=True)
     P.close()
 
 
@@ -137,6 +161,8 @@ def main():
     ap.add_argument("--nbatch", type=int, nargs="+", default=[1, 6, 64, 256, 1024])
     ap.add_argument("--seq-cap", type=int, default=16)
     ap.add_argument("--legs", nargs="+", default=["unbatched", "concurrent4", "batched"])
+    ap.add_argument("--cos-modes", type=int, nargs="+", default=[0], choices=[0, 1, 2])
+    ap.add_argument("--identity", action="store_true")
     a = ap.parse_args()
     (run_cv if a.mode == "cv" else run_sweep)(a)
 
