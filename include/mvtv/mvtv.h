@@ -280,6 +280,42 @@ mvtv_status mvtv_problem_set_scattered(mvtv_problem* prob, const double* axes, c
                                        const double* y, int64_t* mesh_index_out);
 /* mbs_predict (rcpp…/solvers.cpp:161-165): O(data) theta of the resident state, fits [n] */
 mvtv_status mvtv_predict(mvtv_problem* prob, const double* axes, const double* data, int64_t n, double* fits);
+/* The whole k-fold CV of mbs_impl (rcpp…/solvers.cpp:305-376) for a mesh mvtv_problem_batch_ok admits, in one call:
+ * the nearest-node map of the n points (one pass, as mvtv_nearest), every member's W, O^T y and constant start, all
+ * paths as mvtv_path_batch runs them, and the test MSEs, on the device. Member 0 is the final path on all n points;
+ * with folds >= 2, member f + 1 is trained on the points with fold[i] != f: members = 1 + (folds >= 2 ? folds : 0).
+ * A member's W and O^T y are what create_cache_objects gives on its training subset, O^T y summed per node in data
+ * order (bit-identical to mvtv_problem_set_scattered on that subset). Every member runs mvtv_path_batch's path on the
+ * shared grid `lambdas` from theta = theta0[member], u = 0, rho = rho_init: variant B with (theta, u, rho) carried
+ * from lambda to lambda, the theta-solver kinds of mvtv_problem_batch_cosine (each member's kind, mean(W) and std(W)
+ * from mvtv_path_batch's own scan of the W built here), the same honoured options, per-(member, lambda) stats and
+ * return status (MVTV_MAXITER, MVTV_PCG_NOT_CONVERGED under pcg_strict).
+ *   mse_mat[l, f]  = mean over the points with fold[i] == f of (theta_{f+1,l}[node_i] - y_i)^2   (test_mse, :278-288);
+ *                    with folds <= 1 the one column is member 0's mean over all points against y (:413)
+ *   model_mses[l]  = member 0's mean over all points against ref (the path models' mbs_mse, :214)
+ * each a deterministic sum within (k + 4) 2^-53 relative of the exact mean of its k terms. The call does not select a
+ * lambda. prob supplies the geometry, the device and the stream; its own data and resident state are not touched.
+ * Host <-> device traffic: the inputs once, the per-lambda poll of mvtv_path_batch, under a batch_cosine mode the
+ * members' W for that scan, and one download of the results asked for.
+ * MVTV_BAD_ARG, before any launch, for: everything mvtv_path_batch refuses (except SPECTRAL with a member whose W is
+ * not I, found after the setup kernels); a NaN or infinite coordinate or axis value; folds >= 2 with fold NULL; a label
+ * outside [0, folds); a fold with no test point; a member with no training point; n < 1 or n >= 2^32.
+ * MVTV_OUT_OF_MEMORY when the problem's batch buffer cannot grow (the problem stays usable). */
+mvtv_status mvtv_cv_batch(mvtv_problem* prob, const mvtv_admm_opts* opts,
+                          const double* axes, const double* data, int64_t n, const double* y, /* as mvtv_problem_set_scattered */
+                          const int32_t* fold,      /* [n] labels in [0, folds); may be NULL when folds <= 1 */
+                          int32_t folds,
+                          const double* ref,        /* [n] what model_mses is taken against (ftrue); NULL: y */
+                          const double* lambdas, int32_t n_lambda,   /* one grid, shared by every member */
+                          const double* theta0,     /* [members] each member's constant start; NULL: the mean of its y, summed in data order */
+                          double rho_init,          /* NaN: lambdas[0] / 5 (rcpp…/solvers.cpp:209) */
+                          double* mse_mat_out,      /* [n_lambda x max(folds, 1)], lambda-major */
+                          double* model_mses_out,   /* [n_lambda], may be NULL */
+                          double* thetas_out,       /* [n_lambda x N] the final path, may be NULL */
+                          double* fold_thetas_out,  /* [folds x n_lambda x N], may be NULL (tests) */
+                          double* rhos_out,         /* [members x n_lambda], may be NULL */
+                          int64_t* mesh_index_out,  /* [n], may be NULL */
+                          mvtv_admm_stats* stats);  /* [members x n_lambda], may be NULL */
 
 /* ---- operators (inits.D*theta, inits.Dt*v, spcrosses*x, spsolve(spcrosses, b):
  *      rcpp…/solvers.cpp:112-126) ----------------------------------------------------- */

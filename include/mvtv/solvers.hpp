@@ -128,10 +128,21 @@ struct mbs_impl_result {
     int64_t lambda_minmse_ind = 0;   // 1-based, as R
     vec cv_mses;                  // "cv.mses"
 };
-// mbs_impl (:305-376). mesh, ftrue, lambdas may be null (R's NULL). seed: kfoldinds.
+// batched: the fold loop and the final mbs_path run as one mvtv_cv_batch call, every member's whole path in one
+// workgroup (meshes mvtv_problem_batch_ok admits: at most 4096 nodes, p = 4: 1296; tensor-product `mesh` only;
+// std::invalid_argument otherwise). batch_cosine: the mvtv_problem_batch_cosine mode of those fits (0, 1 or 2).
+// The models of final_path then carry theta_hat, fitted and rhohat but an empty uhat: the batched fits keep u on
+// the device and mvtv_cv_batch returns none. Selection and the folds <= 1 refit (mbs_fit_optimal, on the matrix
+// crossO + rho crossD with the rho the final path carried into its last lambda) are unchanged; `verbose` prints
+// nothing for the batched paths.
+struct mbs_impl_options {
+    bool batched = false;
+    int batch_cosine = 0;
+};
+// mbs_impl (:305-376). mesh, ftrue, lambdas may be null (R's NULL). seed: kfoldinds. options: may be null (defaults).
 mbs_impl_result mbs_impl(const mat& data, const vec& y, const vec& m, const mat* mesh, int n_lambda,
                          const vec* ftrue, const vec* lambdas, int folds, bool verbose = false, uint64_t seed = 0,
-                         int device = 0);
+                         int device = 0, const mbs_impl_options* options = nullptr);
 
 // ---- variant A: the research code's API, cpp-code/solvers.hpp ------------------------------------
 // Its own setup constants: EPS = 0.01 (cpp-code/solvers.hpp:13, utils.hpp), TOL = 1e-3.

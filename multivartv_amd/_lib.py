@@ -103,6 +103,9 @@ SIGNATURES = {
     "mvtv_nearest": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int64, C.POINTER(C.c_int64)]),
     "mvtv_problem_set_scattered": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int64, _dp, C.POINTER(C.c_int64)]),
     "mvtv_predict": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int64, _dp]),
+    "mvtv_cv_batch": (C.c_int, [C.c_void_p, C.POINTER(AdmmOpts), _dp, _dp, C.c_int64, _dp, C.POINTER(C.c_int32),
+                                C.c_int32, _dp, _dp, C.c_int32, _dp, C.c_double, _dp, _dp, _dp, _dp, _dp,
+                                C.POINTER(C.c_int64), C.POINTER(AdmmStats)]),
     "mvtv_apply_D": (C.c_int, [C.c_void_p, _dp, _dp]),
     "mvtv_apply_Dt": (C.c_int, [C.c_void_p, _dp, _dp]),
     "mvtv_apply_A": (C.c_int, [C.c_void_p, C.c_double, _dp, _dp]),
@@ -387,6 +390,50 @@ class Problem:
         out = np.empty(n)
         _check(lib().mvtv_predict(self._h, _ptr(ax), d.ctypes.data_as(_dp), n, _ptr(out)))
         return out
+
+    def cv_batch(self, axes, data, y, lambdas, fold=None, folds=1, ref=None, theta0=None, rho_init=None,
+                 want_thetas=True, want_fold_thetas=False, **opts):
+        """The whole k-fold CV of a batch-admitted mesh in one call on the device (mvtv_cv_batch): the nearest-node map,
+        every member's W / O^T y / constant start, all paths as path_batch runs them, and the test MSEs. Member 0 is
+        the final path on all points, member f + 1 is trained on the points with fold != f (folds >= 2). lambdas [n]:
+        one grid for every member; theta0 [members] or None (each member's mean of y, summed in data order); rho_init
+        None: lambdas[0] / 5; ref [len(y)] or None (y): what model_mses is taken against. Returns a dict: mse_mat
+        [n x max(folds, 1)], model_mses [n], thetas [n x N] or None, fold_thetas [folds x n x N] or None, rhos
+        [members x n], stats [members][n], mesh_index [len(y)], status (MVTV_MAXITER when some (member, lambda) hit
+        max_counter)."""
+        o = default_opts(opts.pop("variant", VARIANT_RCPP), **opts)
+        ax, d, n = self._axes_data(axes, data)
+        yy = _f64(y, n)
+        folds = int(folds)
+        nf = folds if folds >= 2 else 0
+        B = 1 + nf
+        lab = None
+        if nf:
+            if fold is None:
+                raise ValueError("folds >= 2 needs the fold labels")
+            lab = np.ascontiguousarray(np.asarray(fold).ravel(), dtype=np.int32)
+            if lab.size != n or not np.array_equal(lab, np.asarray(fold).ravel()):
+                raise ValueError(f"fold must hold {n} integer labels")
+        rf = None if ref is None else _f64(ref, n)
+        lam = _f64(lambdas)
+        nl = lam.size
+        th0 = None if theta0 is None else _f64(theta0, B)
+        mse_mat = np.empty((nl, max(nf, 1)))
+        model_mses = np.empty(nl)
+        thetas = np.empty((nl, self.N)) if want_thetas else None
+        fold_thetas = np.empty((nf, nl, self.N)) if want_fold_thetas else None
+        rhos = np.empty((B, nl))
+        idx = np.empty(n, dtype=np.int64)
+        sts = (AdmmStats * max(B * nl, 1))()
+        s = lib().mvtv_cv_batch(self._h, C.byref(o), _ptr(ax), d.ctypes.data_as(_dp), n, _ptr(yy),
+                                None if lab is None else lab.ctypes.data_as(C.POINTER(C.c_int32)), folds, _ptr(rf),
+                                _ptr(lam), nl, _ptr(th0), math.nan if rho_init is None else float(rho_init),
+                                _ptr(mse_mat), _ptr(model_mses), _ptr(thetas), _ptr(fold_thetas), _ptr(rhos),
+                                idx.ctypes.data_as(C.POINTER(C.c_int64)), sts)
+        if s not in (MVTV_OK, MVTV_MAXITER):
+            _check(s)
+        return dict(mse_mat=mse_mat, model_mses=model_mses, thetas=thetas, fold_thetas=fold_thetas, rhos=rhos,
+                    stats=[[sts[b * nl + i].as_dict() for i in range(nl)] for b in range(B)], mesh_index=idx, status=s)
 
     # ---- operators --------------------------------------------------------------------------
     def apply_D(self, theta):

@@ -2159,17 +2159,12 @@ mvtv_status mvtv_solve_batch(mvtv_problem* P, int32_t nbatch, const double* sigm
     return MVTV_OK;
 }
 
-// Many independent fits on the problem's mesh, each member's whole path in one workgroup (mvtv_small.hip,
-// mvtv_small_cos.hip). The lambda loop is here: per lambda the launches of the loop kernels (one per member kind
-// present) are enqueued two rounds at a time and the device counter of members that have not finished that lambda is
-// read after each pair.
-mvtv_status mvtv_path_batch(mvtv_problem* P, const mvtv_admm_opts* opts, int32_t nbatch, const double* oty,
-                            const double* wdiag, const double* lambdas, int32_t n_lambda, const double* theta_init,
-                            const double* rho_init, double* thetas_out, double* u_out, double* rhos_out,
-                            mvtv_admm_stats* stats) {
-    if (!P || !opts || !oty || !lambdas || !theta_init || !rho_init) return fail(MVTV_BAD_ARG, "null argument");
-    const auto t0 = std::chrono::steady_clock::now();
-    const mvtv_admm_opts& o = *opts;
+}  // extern "C"
+
+namespace {
+// ---- what mvtv_path_batch and mvtv_cv_batch share: the checks, the members' kinds, the lambda loop and the stats ----
+// the refusals that depend on the problem, the options and the counts alone
+mvtv_status batch_check(const mvtv_problem* P, const mvtv_admm_opts& o, int64_t nbatch, int32_t n_lambda) {
     if (!mvtv_problem_batch_ok(P))
         return fail(MVTV_BAD_ARG, "batched fits need one GPU's whole mesh of at most 4096 nodes (p = 4: 1296)");
     if (o.variant != MVTV_VARIANT_RCPP) return fail(MVTV_BAD_ARG, "batched fits run variant B only");
@@ -2185,14 +2180,12 @@ mvtv_status mvtv_path_batch(mvtv_problem* P, const mvtv_admm_opts* opts, int32_t
     }
     if (!std::isnan(o.sigma)) return fail(MVTV_BAD_ARG, "batched fits take the matrix scalar rho (sigma must be NaN)");
     if (nbatch < 1 || n_lambda < 1) return fail(MVTV_BAD_ARG, "nbatch and n_lambda must be >= 1");
-    const size_t N = P->g.N, nbN = size_t(P->g.nb) * N, B = size_t(nbatch), NL = size_t(n_lambda);
-    for (size_t i = 0; i < B * NL; ++i)
-        if (!(lambdas[i] >= 0.0)) return fail(MVTV_BAD_ARG, "lambda must be >= 0");
-    for (size_t b = 0; b < B; ++b)
-        if (!(rho_init[b] > 0.0) || std::isinf(rho_init[b])) return fail(MVTV_BAD_ARG, "rho_init must be positive and finite");
-    // the validation scan of W also gives each member's kind (a row of all ones is W = I) and mean(W), std(W)
-    std::vector<int32_t> kind;
-    std::vector<double> wstat;
+    return MVTV_OK;
+}
+
+// the validation scan of W also gives each member's kind (a row of all ones is W = I) and mean(W), std(W)
+mvtv_status batch_scan_w(const double* wdiag, size_t B, size_t N, int cosm, std::vector<int32_t>& kind,
+                         std::vector<double>& wstat) {
     if (cosm > 0) {
         kind.assign(B, SMALL_KIND_COS);
         wstat.assign(2 * B, 0.0);
@@ -2218,10 +2211,15 @@ mvtv_status mvtv_path_batch(mvtv_problem* P, const mvtv_admm_opts* opts, int32_t
                 wstat[2 * b + 1] = std::sqrt(std::max(0.0, sum2 / double(N) - mean * mean));
             }
         }
-    bool has[3] = {cosm == 0, false, false};
+    return MVTV_OK;
+}
+
+// the kernel each member runs under the problem's batch_cosine mode and opts.theta_solver; has[k]: kind k is present
+mvtv_status batch_kinds(mvtv_problem* P, const mvtv_admm_opts& o, std::vector<int32_t>& kind, bool (&has)[3]) {
+    const int cosm = P->batch_cos;
+    has[0] = cosm == 0, has[1] = has[2] = false;
     if (cosm > 0) {
-        for (size_t b = 0; b < B; ++b) {
-            int32_t& k = kind[b];
+        for (int32_t& k : kind) {
             if (o.theta_solver == MVTV_SOLVER_SPECTRAL && k != SMALL_KIND_COS)
                 return fail(MVTV_BAD_ARG, "batched fits: SPECTRAL needs W = I for every member");
             if (o.theta_solver == MVTV_SOLVER_PCG) k = SMALL_KIND_JACOBI;
@@ -2231,54 +2229,78 @@ mvtv_status mvtv_path_batch(mvtv_problem* P, const mvtv_admm_opts* opts, int32_t
         }
         MVTV_TRY(cos_plan_setup(P));
     }
-    DeviceGuard dg(P->device);
-    double *d_oty = nullptr, *d_w = nullptr, *d_lam = nullptr, *d_theta = nullptr, *d_z = nullptr, *d_gag = nullptr,
-           *d_thetas = nullptr, *d_wstat = nullptr;
-    SmallCtl *d_ctl = nullptr, *d_log = nullptr;
-    int32_t *d_rem = nullptr, *d_kind = nullptr;
-    BatchArena ar{P};
-    ar.add(&d_oty, B * N);
-    if (wdiag) ar.add(&d_w, B * N);
-    ar.add(&d_lam, B * NL);
-    ar.add(&d_theta, B * N);
-    ar.add(&d_z, B * nbN);
-    ar.add(&d_gag, B * 2 * N);
-    if (thetas_out) ar.add(&d_thetas, B * NL * N);
-    ar.add(&d_ctl, B);
-    ar.add(&d_log, B * NL);
-    ar.add(&d_rem, NL);
-    if (cosm > 0) {
-        ar.add(&d_kind, B);
-        ar.add(&d_wstat, 2 * B);
+    return MVTV_OK;
+}
+
+// the members' device-resident inputs and state, carved from the problem's batch arena
+struct BatchDev {
+    double *oty = nullptr, *w = nullptr, *lam = nullptr, *theta = nullptr, *z = nullptr, *gag = nullptr,
+           *thetas = nullptr, *wstat = nullptr;
+    SmallCtl *ctl = nullptr, *log = nullptr;
+    int32_t *rem = nullptr, *kind = nullptr;
+};
+
+void batch_arena_add(BatchArena& ar, BatchDev& d, const mvtv_problem* P, size_t B, size_t NL, bool with_w,
+                     bool with_thetas) {
+    const size_t N = P->g.N, nbN = size_t(P->g.nb) * N;
+    ar.add(&d.oty, B * N);
+    if (with_w) ar.add(&d.w, B * N);
+    ar.add(&d.lam, B * NL);
+    ar.add(&d.theta, B * N);
+    ar.add(&d.z, B * nbN);
+    ar.add(&d.gag, B * 2 * N);
+    if (with_thetas) ar.add(&d.thetas, B * NL * N);
+    ar.add(&d.ctl, B);
+    ar.add(&d.log, B * NL);
+    ar.add(&d.rem, NL);
+    if (P->batch_cos > 0) {
+        ar.add(&d.kind, B);
+        ar.add(&d.wstat, 2 * B);
     }
-    MVTV_TRY(ar.commit());
-    std::vector<SmallCtl> ctl(B);
+}
+
+// u0 = 0 (z = 0), every member's control block from its rho_init, the unfinished-member counters, the kinds. The
+// copies are asynchronous: hs, kind and wstat must outlive the caller's next stream synchronisation.
+struct BatchHostState {
+    std::vector<SmallCtl> ctl;
+    std::vector<int32_t> rem;
+};
+mvtv_status batch_upload_state(mvtv_problem* P, const BatchDev& d, size_t B, size_t NL, const double* rho_init,
+                               const std::vector<int32_t>& kind, const std::vector<double>& wstat, BatchHostState& hs) {
+    const size_t nbN = size_t(P->g.nb) * P->g.N;
+    std::vector<SmallCtl>& ctl = hs.ctl;
+    ctl.resize(B);
     for (size_t b = 0; b < B; ++b) {
         ctl[b] = SmallCtl{};
         ctl[b].cur_l = -1;
         ctl[b].rho = rho_init[b];
         ctl[b].c = 1.0;   // u0 = 0: z = 0, t_z = 0
     }
-    const std::vector<int32_t> rem(NL, nbatch);
+    hs.rem.assign(NL, int32_t(B));
+    const std::vector<int32_t>& rem = hs.rem;
     hipStream_t s = P->stream;
-    HIP_TRY(hipMemcpyAsync(d_oty, oty, B * N * sizeof(double), hipMemcpyHostToDevice, s));
-    if (wdiag) HIP_TRY(hipMemcpyAsync(d_w, wdiag, B * N * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_lam, lambdas, B * NL * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_theta, theta_init, B * N * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(d_z, 0, B * nbN * sizeof(double), s));
-    HIP_TRY(hipMemcpyAsync(d_ctl, ctl.data(), B * sizeof(SmallCtl), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_rem, rem.data(), NL * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    if (cosm > 0) {
-        HIP_TRY(hipMemcpyAsync(d_kind, kind.data(), B * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_wstat, wstat.data(), 2 * B * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(d.z, 0, B * nbN * sizeof(double), s));
+    HIP_TRY(hipMemcpyAsync(d.ctl, ctl.data(), B * sizeof(SmallCtl), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d.rem, rem.data(), NL * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (P->batch_cos > 0) {
+        HIP_TRY(hipMemcpyAsync(d.kind, kind.data(), B * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d.wstat, wstat.data(), 2 * B * sizeof(double), hipMemcpyHostToDevice, s));
     }
+    return MVTV_OK;
+}
 
+// The lambda loop over device-resident members: per lambda the launches of the loop kernels (one per member kind
+// present) are enqueued two rounds at a time and the device counter of members that have not finished that lambda is
+// read after each pair.
+mvtv_status batch_loop(mvtv_problem* P, const mvtv_admm_opts& o, int32_t nbatch, int32_t n_lambda, const BatchDev& d,
+                       const bool (&has)[3]) {
+    hipStream_t s = P->stream;
     Geom g = P->g;
     g.eaos = 0;
     SmallArgs a{};
-    a.oty = d_oty, a.wdiag = d_w, a.lambdas = d_lam, a.theta = d_theta, a.z = d_z, a.gag = d_gag;
-    a.ctl = d_ctl, a.log = d_log, a.thetas_out = d_thetas, a.remaining = d_rem;
-    a.kind = d_kind, a.wstat = d_wstat;
+    a.oty = d.oty, a.wdiag = d.w, a.lambdas = d.lam, a.theta = d.theta, a.z = d.z, a.gag = d.gag;
+    a.ctl = d.ctl, a.log = d.log, a.thetas_out = d.thetas, a.remaining = d.rem;
+    a.kind = d.kind, a.wstat = d.wstat;
     a.n_lambda = n_lambda;
     a.fixed_iters = o.fixed_iters;
     a.max_counter = variant_maxc(o);
@@ -2287,7 +2309,7 @@ mvtv_status mvtv_path_batch(mvtv_problem* P, const mvtv_admm_opts* opts, int32_t
     a.tol = variant_tol(o);
     const double rtol = o.pcg_rtol > 0 ? o.pcg_rtol : 1e-10;
     a.rtol2 = rtol * rtol;
-    a.sqrtN = std::sqrt(double(N));
+    a.sqrtN = std::sqrt(double(P->g.N));
     a.sqrtE = std::sqrt(double(P->E));
     for (int k = 0; k < P->g.nb; ++k) a.sp[k] = P->sprime[k];
     // launches that can be needed for one lambda: the iteration bound in chunks, and the pair's second
@@ -2303,17 +2325,88 @@ mvtv_status mvtv_path_batch(mvtv_problem* P, const mvtv_admm_opts* opts, int32_t
                 if (has[SMALL_KIND_COS]) HIP_TRY(launch_admm_cos(g, P->cos, s, nbatch, a, false));
                 if (has[SMALL_KIND_COS_PCG]) HIP_TRY(launch_admm_cos(g, P->cos, s, nbatch, a, true));
             }
-            HIP_TRY(hipMemcpyAsync(&left, d_rem + li, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(&left, d.rem + li, sizeof(int32_t), hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
         }
     }
+    return MVTV_OK;
+}
+
+// the per-(member, lambda) control blocks as rhos and stats; the call's return status
+mvtv_status batch_stats(const mvtv_problem* P, const std::vector<SmallCtl>& log, size_t NL,
+                        const std::vector<int32_t>& kind, double seconds, double* rhos_out, mvtv_admm_stats* stats) {
+    mvtv_status worst = MVTV_OK;
+    for (size_t i = 0; i < log.size(); ++i) {
+        const SmallCtl& c = log[i];
+        if (c.status == MVTV_PCG_NOT_CONVERGED) worst = MVTV_PCG_NOT_CONVERGED;
+        else if (c.status == MVTV_MAXITER && worst == MVTV_OK) worst = MVTV_MAXITER;
+        if (rhos_out) rhos_out[i] = c.rho;
+        if (stats) {
+            mvtv_admm_stats S{};
+            S.iters = c.it;
+            S.status = c.status;
+            S.r_norm = c.primal;
+            S.s_norm = c.dual;
+            S.eps_pri = c.eps_p;
+            S.eps_dual = c.eps_d;
+            S.rho = c.rho;
+            S.pcg_iters = c.pcg_iters;
+            S.pcg_iters_max = c.pcg_max;
+            S.pcg_unconverged = c.pcg_unconv;
+            S.seconds = seconds;
+            const int32_t k = P->batch_cos > 0 ? kind[i / NL] : int32_t(SMALL_KIND_JACOBI);
+            S.theta_solver = k == SMALL_KIND_COS ? MVTV_SOLVER_SPECTRAL
+                                                 : (k == SMALL_KIND_COS_PCG ? MVTV_SOLVER_PCG_SPECTRAL : MVTV_SOLVER_PCG);
+            stats[i] = S;
+        }
+    }
+    if (worst == MVTV_PCG_NOT_CONVERGED) fail(worst, "PCG hit pcg_max_iter");
+    return worst;
+}
+}  // namespace
+
+extern "C" {
+
+// Many independent fits on the problem's mesh, each member's whole path in one workgroup (mvtv_small.hip,
+// mvtv_small_cos.hip): the members' inputs go up, batch_loop runs them, the results come down.
+mvtv_status mvtv_path_batch(mvtv_problem* P, const mvtv_admm_opts* opts, int32_t nbatch, const double* oty,
+                            const double* wdiag, const double* lambdas, int32_t n_lambda, const double* theta_init,
+                            const double* rho_init, double* thetas_out, double* u_out, double* rhos_out,
+                            mvtv_admm_stats* stats) {
+    if (!P || !opts || !oty || !lambdas || !theta_init || !rho_init) return fail(MVTV_BAD_ARG, "null argument");
+    const auto t0 = std::chrono::steady_clock::now();
+    const mvtv_admm_opts& o = *opts;
+    MVTV_TRY(batch_check(P, o, nbatch, n_lambda));
+    const size_t N = P->g.N, nbN = size_t(P->g.nb) * N, B = size_t(nbatch), NL = size_t(n_lambda);
+    for (size_t i = 0; i < B * NL; ++i)
+        if (!(lambdas[i] >= 0.0)) return fail(MVTV_BAD_ARG, "lambda must be >= 0");
+    for (size_t b = 0; b < B; ++b)
+        if (!(rho_init[b] > 0.0) || std::isinf(rho_init[b])) return fail(MVTV_BAD_ARG, "rho_init must be positive and finite");
+    std::vector<int32_t> kind;
+    std::vector<double> wstat;
+    MVTV_TRY(batch_scan_w(wdiag, B, N, P->batch_cos, kind, wstat));
+    bool has[3];
+    MVTV_TRY(batch_kinds(P, o, kind, has));
+    DeviceGuard dg(P->device);
+    BatchDev d;
+    BatchArena ar{P};
+    batch_arena_add(ar, d, P, B, NL, wdiag != nullptr, thetas_out != nullptr);
+    MVTV_TRY(ar.commit());
+    hipStream_t s = P->stream;
+    HIP_TRY(hipMemcpyAsync(d.oty, oty, B * N * sizeof(double), hipMemcpyHostToDevice, s));
+    if (wdiag) HIP_TRY(hipMemcpyAsync(d.w, wdiag, B * N * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d.lam, lambdas, B * NL * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d.theta, theta_init, B * N * sizeof(double), hipMemcpyHostToDevice, s));
+    BatchHostState hs;
+    MVTV_TRY(batch_upload_state(P, d, B, NL, rho_init, kind, wstat, hs));
+    MVTV_TRY(batch_loop(P, o, nbatch, n_lambda, d, has));
     std::vector<SmallCtl> log(B * NL);
-    HIP_TRY(hipMemcpyAsync(log.data(), d_log, B * NL * sizeof(SmallCtl), hipMemcpyDeviceToHost, s));
-    if (thetas_out) HIP_TRY(hipMemcpyAsync(thetas_out, d_thetas, B * NL * N * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(log.data(), d.log, B * NL * sizeof(SmallCtl), hipMemcpyDeviceToHost, s));
+    if (thetas_out) HIP_TRY(hipMemcpyAsync(thetas_out, d.thetas, B * NL * N * sizeof(double), hipMemcpyDeviceToHost, s));
     std::vector<double> z;
     if (u_out) {
         z.resize(B * nbN);
-        HIP_TRY(hipMemcpyAsync(z.data(), d_z, B * nbN * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(z.data(), d.z, B * nbN * sizeof(double), hipMemcpyDeviceToHost, s));
     }
     HIP_TRY(hipStreamSynchronize(s));
     if (u_out) {   // u = -c clamp(z, t_z) on the real edges, blocks in the problem's order, each a column-major reduced grid
@@ -2337,33 +2430,7 @@ mvtv_status mvtv_path_batch(mvtv_problem* P, const mvtv_admm_opts* opts, int32_t
         }
     }
     const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    mvtv_status worst = MVTV_OK;
-    for (size_t i = 0; i < B * NL; ++i) {
-        const SmallCtl& c = log[i];
-        if (c.status == MVTV_PCG_NOT_CONVERGED) worst = MVTV_PCG_NOT_CONVERGED;
-        else if (c.status == MVTV_MAXITER && worst == MVTV_OK) worst = MVTV_MAXITER;
-        if (rhos_out) rhos_out[i] = c.rho;
-        if (stats) {
-            mvtv_admm_stats S{};
-            S.iters = c.it;
-            S.status = c.status;
-            S.r_norm = c.primal;
-            S.s_norm = c.dual;
-            S.eps_pri = c.eps_p;
-            S.eps_dual = c.eps_d;
-            S.rho = c.rho;
-            S.pcg_iters = c.pcg_iters;
-            S.pcg_iters_max = c.pcg_max;
-            S.pcg_unconverged = c.pcg_unconv;
-            S.seconds = seconds;
-            const int32_t k = cosm > 0 ? kind[i / NL] : int32_t(SMALL_KIND_JACOBI);
-            S.theta_solver = k == SMALL_KIND_COS ? MVTV_SOLVER_SPECTRAL
-                                                 : (k == SMALL_KIND_COS_PCG ? MVTV_SOLVER_PCG_SPECTRAL : MVTV_SOLVER_PCG);
-            stats[i] = S;
-        }
-    }
-    if (worst == MVTV_PCG_NOT_CONVERGED) fail(worst, "PCG hit pcg_max_iter");
-    return worst;
+    return batch_stats(P, log, NL, kind, seconds, rhos_out, stats);
 }
 
 mvtv_status mvtv_fitted(mvtv_problem* P, const int64_t* mesh_index, int64_t n, double* fitted) {
@@ -2407,12 +2474,13 @@ struct TmpDev {
 
 // axes (finite, ascending per dim) and data (finite) checked on the host, then axes and data copied over and the
 // nearest node of every point computed into key (and idx when requested)
-mvtv_status nearest_on_device(mvtv_problem* P, const double* axes, const double* data, int64_t n, TmpDev& key,
-                              TmpDev& idx, bool want_idx) {
+// the host checks of a scattered data set: not a slab rank, axes finite and ascending, data finite; *na = the axes'
+// value count, span[j] = axis j's extent
+mvtv_status check_axes_data(const mvtv_problem* P, const double* axes, const double* data, int64_t n, size_t* na_out,
+                            double (&span)[MVTV_MAX_DIMS]) {
     if (P->slab) return fail(MVTV_BAD_ARG, "scattered data on a slab problem: set it up on the whole mesh");
     const int p = P->g.p;
     size_t na = 0;
-    double span[MVTV_MAX_DIMS] = {0, 0, 0, 0};
     for (int j = 0; j < p; ++j) {
         const double* a = axes + na;
         span[j] = a[P->g.m[j] - 1] - a[0];
@@ -2423,6 +2491,16 @@ mvtv_status nearest_on_device(mvtv_problem* P, const double* axes, const double*
     }
     for (int64_t i = 0; i < n * p; ++i)
         if (!std::isfinite(data[i])) return fail(MVTV_BAD_ARG, "NaN or infinite value in data");
+    *na_out = na;
+    return MVTV_OK;
+}
+
+mvtv_status nearest_on_device(mvtv_problem* P, const double* axes, const double* data, int64_t n, TmpDev& key,
+                              TmpDev& idx, bool want_idx) {
+    const int p = P->g.p;
+    size_t na = 0;
+    double span[MVTV_MAX_DIMS] = {0, 0, 0, 0};
+    MVTV_TRY(check_axes_data(P, axes, data, n, &na, span));
     TmpDev daxes, ddata;
     HIP_TRY(hipMalloc(&daxes.p, na * sizeof(double)));
     HIP_TRY(hipMalloc(&ddata.p, size_t(std::max<int64_t>(n * p, 1)) * sizeof(double)));
@@ -2498,6 +2576,132 @@ mvtv_status mvtv_predict(mvtv_problem* P, const double* axes, const double* data
     HIP_TRY(hipMemcpyAsync(fits, out.p, size_t(n) * sizeof(double), hipMemcpyDeviceToHost, P->stream));
     HIP_TRY(hipStreamSynchronize(P->stream));
     return MVTV_OK;
+}
+
+// mbs_impl's whole CV for a batch-admitted mesh (rcpp…/solvers.cpp:305-376 without the lambda selection): one upload
+// of the data, every member set up and scored by the kernels of mvtv_cv.hip, the paths by mvtv_path_batch's loop
+// (batch_loop), one download.
+mvtv_status mvtv_cv_batch(mvtv_problem* P, const mvtv_admm_opts* opts, const double* axes, const double* data, int64_t n,
+                          const double* y, const int32_t* fold, int32_t folds, const double* ref, const double* lambdas,
+                          int32_t n_lambda, const double* theta0, double rho_init, double* mse_mat_out,
+                          double* model_mses_out, double* thetas_out, double* fold_thetas_out, double* rhos_out,
+                          int64_t* mesh_index_out, mvtv_admm_stats* stats) {
+    if (!P || !opts || !axes || !data || !y || !lambdas || !mse_mat_out) return fail(MVTV_BAD_ARG, "null argument");
+    const auto t0 = std::chrono::steady_clock::now();
+    const mvtv_admm_opts& o = *opts;
+    const int32_t nf = folds >= 2 ? folds : 0;   // fold members
+    MVTV_TRY(batch_check(P, o, 1 + int64_t(nf), n_lambda));
+    if (n < 1 || uint64_t(n) >= (uint64_t(1) << 32)) return fail(MVTV_BAD_ARG, "cv_batch: n must be in [1, 2^32)");
+    if (nf > 0 && !fold) return fail(MVTV_BAD_ARG, "cv_batch: folds >= 2 needs the fold labels");
+    if (int64_t(nf) > n) return fail(MVTV_BAD_ARG, "cv_batch: a fold has no test point");
+    const size_t N = P->g.N, B = 1 + size_t(nf), NL = size_t(n_lambda), F = std::max<size_t>(nf, 1);
+    if (B * NL > (size_t(1) << 30)) return fail(MVTV_BAD_ARG, "cv_batch: more than 2^30 (member, lambda) pairs");
+    for (size_t i = 0; i < NL; ++i)
+        if (!(lambdas[i] >= 0.0)) return fail(MVTV_BAD_ARG, "lambda must be >= 0");
+    const double rho0 = std::isnan(rho_init) ? lambdas[0] / 5.0 : rho_init;   // rcpp…/solvers.cpp:209
+    if (!(rho0 > 0.0) || std::isinf(rho0)) return fail(MVTV_BAD_ARG, "rho_init must be positive and finite");
+    std::vector<int64_t> ntest(F, 0);
+    for (int64_t i = 0; nf > 0 && i < n; ++i) {
+        if (fold[i] < 0 || fold[i] >= nf) return fail(MVTV_BAD_ARG, "cv_batch: a fold label outside [0, folds)");
+        ++ntest[size_t(fold[i])];
+    }
+    for (int32_t f = 0; f < nf; ++f) {
+        if (ntest[size_t(f)] == 0) return fail(MVTV_BAD_ARG, "cv_batch: a fold has no test point");
+        if (ntest[size_t(f)] == n) return fail(MVTV_BAD_ARG, "cv_batch: a member has no training point");
+    }
+    const int p = P->g.p;
+    size_t na = 0;
+    double span[MVTV_MAX_DIMS] = {0, 0, 0, 0};
+    MVTV_TRY(check_axes_data(P, axes, data, n, &na, span));
+    // every member's constant start: the caller's, or the mean of its y summed in data order
+    std::vector<double> th0(B);
+    for (size_t b = 0; b < B; ++b) {
+        if (theta0) {
+            th0[b] = theta0[b];
+            continue;
+        }
+        double sum = 0.0;
+        for (int64_t i = 0; i < n; ++i)
+            if (b == 0 || fold[i] != int32_t(b) - 1) sum += y[i];
+        th0[b] = sum / double(b == 0 ? n : n - ntest[b - 1]);
+    }
+    const std::vector<double> rho(B, rho0);
+    std::vector<double> lam(B * NL);
+    for (size_t b = 0; b < B; ++b) std::copy(lambdas, lambdas + NL, lam.begin() + b * NL);
+    const int cosm = P->batch_cos;
+    DeviceGuard dg(P->device);
+    if (cosm > 0) MVTV_TRY(cos_plan_setup(P));
+    size_t tmp_bytes = 0;
+    HIP_TRY(cv_sort_temp_bytes(n, P->g.N, &tmp_bytes));
+    BatchDev d;
+    double *d_axes = nullptr, *d_data = nullptr, *d_y = nullptr, *d_ref = nullptr, *d_th0 = nullptr, *d_mse = nullptr,
+           *d_mmse = nullptr;
+    int32_t* d_fold = nullptr;
+    uint32_t *d_key = nullptr, *d_pos = nullptr, *d_key2 = nullptr, *d_pos2 = nullptr;
+    int64_t* d_idx = nullptr;
+    char* d_tmp = nullptr;
+    BatchArena ar{P};
+    batch_arena_add(ar, d, P, B, NL, true, true);
+    ar.add(&d_axes, na);
+    ar.add(&d_data, size_t(n) * size_t(p));
+    ar.add(&d_y, size_t(n));
+    if (ref) ar.add(&d_ref, size_t(n));
+    if (nf > 0) ar.add(&d_fold, size_t(n));
+    ar.add(&d_th0, B);
+    ar.add(&d_mse, NL * F);
+    ar.add(&d_mmse, NL);
+    ar.add(&d_key, size_t(n));
+    ar.add(&d_pos, size_t(n));
+    ar.add(&d_key2, size_t(n));
+    ar.add(&d_pos2, size_t(n));
+    ar.add(&d_idx, size_t(n));
+    ar.add(&d_tmp, tmp_bytes);
+    MVTV_TRY(ar.commit());
+    hipStream_t s = P->stream;
+    // inputs up, once
+    HIP_TRY(hipMemcpyAsync(d_axes, axes, na * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_data, data, size_t(n) * size_t(p) * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_y, y, size_t(n) * sizeof(double), hipMemcpyHostToDevice, s));
+    if (ref) HIP_TRY(hipMemcpyAsync(d_ref, ref, size_t(n) * sizeof(double), hipMemcpyHostToDevice, s));
+    if (nf > 0) HIP_TRY(hipMemcpyAsync(d_fold, fold, size_t(n) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_th0, th0.data(), B * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d.lam, lam.data(), B * NL * sizeof(double), hipMemcpyHostToDevice, s));
+    // member setup: the nearest-node map once, one stable sort, every member's O^T y and W, theta_0
+    uint32_t m[MVTV_MAX_DIMS];
+    for (int j = 0; j < p; ++j) m[j] = P->g.m[j];
+    HIP_TRY(launch_cv_fill(s, d_pos, n, d_th0, d.theta, P->g.N, int32_t(B)));
+    HIP_TRY(launch_nearest(s, p, m, d_axes, span, d_data, n, d_key, d_idx));
+    HIP_TRY(launch_cv_fold_sums(s, d_key, d_pos, d_key2, d_pos2, d_tmp, tmp_bytes, d_y, d_fold, n, P->g.N, int32_t(B),
+                                d.oty, d.w));
+    // the cosine modes' member data from the host scan of mvtv_path_batch over the W just built
+    std::vector<int32_t> kind;
+    std::vector<double> wstat, w_host;
+    bool has[3];
+    if (cosm > 0) {
+        w_host.resize(B * N);
+        HIP_TRY(hipMemcpyAsync(w_host.data(), d.w, B * N * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        MVTV_TRY(batch_scan_w(w_host.data(), B, N, cosm, kind, wstat));
+    }
+    MVTV_TRY(batch_kinds(P, o, kind, has));
+    BatchHostState hs;
+    MVTV_TRY(batch_upload_state(P, d, B, NL, rho.data(), kind, wstat, hs));
+    MVTV_TRY(batch_loop(P, o, int32_t(B), n_lambda, d, has));
+    HIP_TRY(launch_cv_mse(s, d.thetas, d_idx, d_y, ref ? d_ref : d_y, d_fold, n, P->g.N, n_lambda, int32_t(B), d_mse,
+                          d_mmse));
+    // one download
+    std::vector<SmallCtl> log(B * NL);
+    HIP_TRY(hipMemcpyAsync(log.data(), d.log, B * NL * sizeof(SmallCtl), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(mse_mat_out, d_mse, NL * F * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (model_mses_out) HIP_TRY(hipMemcpyAsync(model_mses_out, d_mmse, NL * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (thetas_out) HIP_TRY(hipMemcpyAsync(thetas_out, d.thetas, NL * N * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (fold_thetas_out && nf > 0)
+        HIP_TRY(hipMemcpyAsync(fold_thetas_out, d.thetas + NL * N, size_t(nf) * NL * N * sizeof(double),
+                               hipMemcpyDeviceToHost, s));
+    if (mesh_index_out) HIP_TRY(hipMemcpyAsync(mesh_index_out, d_idx, size_t(n) * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return batch_stats(P, log, NL, kind, seconds, rhos_out, stats);
 }
 
 // ------------------------------------------------------------------------------ operators

@@ -554,4 +554,22 @@ hipError_t launch_nearest(hipStream_t s, int p, const uint32_t* m, const double*
 hipError_t launch_scatter_sums(hipStream_t s, uint32_t* key, const double* y, int64_t n, uint32_t N, double* oty,
                                double* wdiag, unsigned long long* nruns);
 
+// ---- the CV of a batched fit on the device (mvtv_cv.hip, mvtv_cv_batch) ---------------------------------------
+// bytes of scratch the stable sort of n (node, position) pairs with nodes < N takes
+hipError_t cv_sort_temp_bytes(int64_t n, uint32_t N, size_t* bytes);
+// pos[i] = i, i < n, and theta[b][.] = theta0[b], b < members
+hipError_t launch_cv_fill(hipStream_t s, uint32_t* pos, int64_t n, const double* theta0, double* theta, uint32_t N,
+                          int32_t members);
+// key (each point's node), pos (consumed) -> key2, pos2 sorted by node, then every member's O^T y and W [members][N]:
+// member 0 over all points, member b over the points with fold[i] != b - 1 (fold may be nullptr when members == 1),
+// each node's sum in data order
+hipError_t launch_cv_fold_sums(hipStream_t s, uint32_t* key, uint32_t* pos, uint32_t* key2, uint32_t* pos2, void* tmp,
+                               size_t tmp_bytes, const double* y, const int32_t* fold, int64_t n, uint32_t N,
+                               int32_t members, double* oty, double* wdiag);
+// thetas [members][n_lambda][N] -> mse_mat [n_lambda][max(members - 1, 1)] (member b >= 1 over fold b - 1 against y;
+// members == 1: member 0 over all points against y) and model_mses [n_lambda] (member 0 over all points against ref)
+hipError_t launch_cv_mse(hipStream_t s, const double* thetas, const int64_t* node, const double* y, const double* ref,
+                         const int32_t* fold, int64_t n, uint32_t N, int32_t n_lambda, int32_t members, double* mse_mat,
+                         double* model_mses);
+
 }  // namespace mvtv

@@ -10,6 +10,10 @@
 //   n_lambda, lambda_minmse_ind, N, n   (int64)
 //   lambdas[n_lambda], cv_mses[n_lambda], model_mses[n_lambda], theta_hat[N], fitted[n], residuals[n]
 //
+// `mvtv_mbs --batched[=MODE] <input> <output>`: the same mbs_impl with mbs_impl_options::batched, the whole CV as one
+// mvtv_cv_batch call (meshes of at most 4096 nodes, p = 4: 1296); MODE is the batch_cosine mode 0, 1 or 2 (default 0).
+// Same input and output formats.
+//
 // `mvtv_mbs --cpp <input> <output>`: variant A's mbs (cpp-code/solvers.cpp:277-310) instead. Same input
 // (hdr[6] = 1 selects the corrected CV, 0 the reference's); output:
 //   n_lambda, best (0-based), N, n   (int64)
@@ -34,12 +38,19 @@ int main(int argc, char** argv) {
     int mode = 0;   // 0 mbs_impl (B), 1 mbs (A), 2 mbs_one without cache (A)
     if (argc == 4 && std::string(argv[1]) == "--cpp") mode = 1;
     if (argc == 4 && std::string(argv[1]) == "--cpp-one") mode = 2;
-    if (mode) {
+    mvtv::mbs_impl_options bopt;
+    if (argc == 4 && std::string(argv[1]).rfind("--batched", 0) == 0) {
+        const std::string a = argv[1];
+        bopt.batched = true;
+        if (a.size() == 11 && a[9] == '=' && a[10] >= '0' && a[10] <= '2') bopt.batch_cosine = a[10] - '0';
+        else if (a != "--batched") bopt.batched = false;   // falls through to the usage message
+    }
+    if (mode || bopt.batched) {
         ++argv;
         --argc;
     }
     if (argc != 3) {
-        std::fprintf(stderr, "usage: %s [--cpp | --cpp-one] <input> <output>\n", argv[0]);
+        std::fprintf(stderr, "usage: %s [--cpp | --cpp-one | --batched[=0|1|2]] <input> <output>\n", argv[0]);
         return 2;
     }
     std::FILE* in = std::fopen(argv[1], "rb");
@@ -95,7 +106,7 @@ int main(int argc, char** argv) {
     }
     try {
         const auto R = mvtv::mbs_impl(data, y, m, nullptr, int(nl), nullptr, given ? &lambdas : nullptr, int(folds),
-                                      false, uint64_t(seed), int(dev));
+                                      false, uint64_t(seed), int(dev), &bopt);
         std::FILE* out = std::fopen(argv[2], "wb");
         if (!out) {
             std::perror(argv[2]);

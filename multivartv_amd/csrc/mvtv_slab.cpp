@@ -459,6 +459,9 @@ struct IpcComm final : mvtv_comm {
     size_t stage_words = 0;
     uint64_t stage_gen = 0;
     hipIpcMemHandle_t stage_handle{};
+    // staging buffers outgrown: a peer keeps its mapping of one until it next receives from this rank, so an exported
+    // buffer is freed with the communicator, not when its successor is allocated
+    std::vector<double*> retired;
     struct Mapped { uint64_t gen = 0; char* ptr = nullptr; };
     std::vector<Mapped> mapped;                     // per peer: its staging buffer in this process
     double timeout_s = 300.0;
@@ -473,9 +476,10 @@ struct IpcComm final : mvtv_comm {
 
     ~IpcComm() override {
         close_mappings();
-        if (stage) {
+        if (stage || !retired.empty()) {
             DeviceGuard dg(device);
-            (void)hipFree(stage);
+            if (stage) (void)hipFree(stage);
+            for (double* r : retired) (void)hipFree(r);
         }
         if (shm) munmap(shm, sizeof(IpcShm));
     }
@@ -556,7 +560,7 @@ struct IpcComm final : mvtv_comm {
             words += (outs[i].n + 31) / 32 * 32;
         }
         if (words > stage_words) {
-            if (stage) HIP_TRY(hipFree(stage));
+            if (stage) retired.push_back(stage);
             stage = nullptr;
             stage_words = std::max<size_t>(words, size_t(1) << 20);
             MVTV_TRY(alloc(&stage, stage_words));

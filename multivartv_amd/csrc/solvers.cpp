@@ -397,8 +397,67 @@ void mbs_fit_optimal(const mat& data, const vec& y, const vec& m, mbs_one_object
     mbs_one(data, y, m, best_model, mesh, u, rho, theta, lambdas[best], cache, verbose);
 }
 
+namespace {
+// mbs_impl's fold loop and final mbs_path as one mvtv_cv_batch call (options.batched): fills mse_mat, R.final_path and
+// cache.sp_sigma as the unbatched sequence leaves them
+void mbs_impl_batched(const mat& data, const vec& y, const vec& m, const mat& MESH, const vec& FTRUE, int folds,
+                      uint64_t seed, int batch_cosine, mbs_cache& cache, mat& mse_mat, mbs_impl_result& R) {
+    const auto axes = tensor_axes(MESH, mesh_dims(m));
+    if (axes.empty()) throw std::invalid_argument("mbs_impl: the batched mode needs a tensor-product mesh");
+    if (!mvtv_problem_batch_ok(cache.prob))
+        throw std::invalid_argument("mbs_impl: the batched mode needs a mesh of at most 4096 nodes (p = 4: 1296)");
+    check(mvtv_problem_batch_cosine(cache.prob, batch_cosine));
+    vec flat;
+    for (const auto& a : axes) flat.insert(flat.end(), a.begin(), a.end());
+    const int nf = folds > 1 ? folds : 0;
+    std::vector<int32_t> fi;
+    if (nf)
+        for (int v : kfoldinds(data.n_rows, folds, seed)) fi.push_back(int32_t(v));
+    const size_t nl = R.lambdas.size(), N = size_t(cache.ntheta), n = size_t(data.n_rows), F = size_t(std::max(nf, 1));
+    vec mm(nl * F), model_mses(nl), thetas(nl * N), rhos((1 + size_t(nf)) * nl);
+    std::vector<int64_t> idx(n);
+    mvtv_admm_opts o;
+    mvtv_default_opts(&o, MVTV_VARIANT_RCPP);
+    // theta0 NULL: every member starts from the sequential mean of its y, as mean() gives
+    const int s = mvtv_cv_batch(cache.prob, &o, flat.data(), data.v.data(), data.n_rows, y.data(),
+                                nf ? fi.data() : nullptr, folds, nf ? y.data() : FTRUE.data(), R.lambdas.data(),
+                                int32_t(nl), nullptr, std::numeric_limits<double>::quiet_NaN(), mm.data(),
+                                model_mses.data(), thetas.data(), nullptr, rhos.data(), idx.data(), nullptr);
+    if (s != MVTV_OK && s != MVTV_MAXITER) check(s);   // B breaks at max_counter and goes on (:129-132)
+    for (size_t i = 0; i < nl; ++i)
+        for (size_t f = 0; f < F; ++f) mse_mat(int64_t(i), int64_t(f)) = mm[i * F + f];
+    mbs_object& out = R.final_path;
+    out.models.clear();
+    out.mses = model_mses;
+    for (size_t i = 0; i < nl; ++i) {
+        mbs_one_object model;
+        model.theta_hat.assign(thetas.begin() + i * N, thetas.begin() + (i + 1) * N);
+        model.fitted.resize(n);
+        for (size_t k = 0; k < n; ++k) model.fitted[k] = model.theta_hat[size_t(idx[k])];
+        model.rhohat = rhos[i];   // member 0
+        // uhat stays empty: the batched fits keep u on the device and mvtv_cv_batch returns none
+        model.mesh = MESH;
+        model.data = data;
+        model.y = y;
+        model.m = m;
+        out.models.push_back(std::move(model));
+    }
+    size_t best = 0;   // fill_output_mbs (:177-184): first minimum
+    for (size_t i = 1; i < nl; ++i)
+        if (out.mses[i] < out.mses[best]) best = i;
+    if (nl) {
+        out.minmse_model = out.models[best];
+        out.minmse = out.mses[best];
+        out.minmse_lambda = R.lambdas[best];
+    }
+    // what mbs_path leaves in the cache (:213): the rho carried into the last lambda
+    cache.sp_sigma = nl >= 2 ? rhos[nl - 2] : R.lambdas[0] / 5.0;
+}
+}  // namespace
+
 mbs_impl_result mbs_impl(const mat& data, const vec& y, const vec& m, const mat* mesh, int n_lambda,
-                         const vec* ftrue, const vec* lambdas, int folds, bool verbose, uint64_t seed, int device) {
+                         const vec* ftrue, const vec* lambdas, int folds, bool verbose, uint64_t seed, int device,
+                         const mbs_impl_options* options) {
     mbs_impl_result R;
     const mat MESH = mesh ? *mesh : create_mesh(data, m);
     const vec deltas = create_deltas(data, m);
@@ -408,7 +467,17 @@ mbs_impl_result mbs_impl(const mat& data, const vec& y, const vec& m, const mat*
     const int nl = int(R.lambdas.size());
     const vec FTRUE = ftrue ? *ftrue : y;
     mat mse_mat(nl, std::max(folds, 1));
-    if (folds <= 1) {
+    if (options && options->batched) {
+        if (nl < 1) throw std::invalid_argument("mbs_impl: the batched mode needs at least one lambda");
+        mbs_impl_batched(data, y, m, MESH, FTRUE, folds, seed, options->batch_cosine, cache, mse_mat, R);
+        R.cv_mses.assign(size_t(nl), 0.0);
+        for (int i = 0; i < nl; ++i) {
+            double s = 0.0;
+            for (int64_t f = 0; f < mse_mat.n_cols; ++f) s += mse_mat(i, f);
+            R.cv_mses[size_t(i)] = folds <= 1 ? mse_mat(i, 0) : s / double(folds);
+        }
+        if (folds <= 1) mbs_fit_optimal(data, y, m, R.best, MESH, R.lambdas, mse_mat, cache, verbose);
+    } else if (folds <= 1) {
         mbs_path(data, y, m, MESH, R.lambdas, FTRUE, R.final_path, cache, verbose);
         const vec t = test_mse(data, y, R.final_path, nl);
         for (int i = 0; i < nl; ++i) mse_mat(i, 0) = t[size_t(i)];

@@ -136,7 +136,7 @@ def assign(n_items: int, world: int, rank: int):
 
 
 def mbs_impl(data, y, m, mesh=None, n_lambda=100, ftrue=None, lambdas=None, folds=1, verbose=False, seed=0,
-             device=None, group=None, _runner=None, concurrent=1, batched=False, batch_cosine=0):
+             device=None, group=None, _runner=None, concurrent=1, batched=False, batch_cosine=0, device_cv=False):
     """rcpp…/solvers.cpp:305-376. Returns the reference's result list as a dict (rank 0; other
     ranks return only 'cv.mses' and 'lambda_minmse_ind').
 
@@ -152,6 +152,12 @@ def mbs_impl(data, y, m, mesh=None, n_lambda=100, ftrue=None, lambdas=None, fold
     (``Problem.batch_ok``) or ``_runner`` is given; ``concurrent`` is ignored. ``batch_cosine`` (0, 1 or 2) is passed to
     ``Problem.batch_cosine`` before that call: the in-workgroup cosine theta-solve for W = I members (1) and as the
     preconditioner of the others' PCG (2); 0, the default, leaves the Jacobi-PCG path as it is.
+
+    ``device_cv`` (with ``batched``): the paths and the fold-MSE matrix come from one ``Problem.cv_batch`` call, which
+    also builds every member's nearest-node map, W and O^T y and scores the folds on the GPU; numpy's member means go
+    in as theta_0, so the fits are those of ``batched=True``. Selection, the folds == 1 refit and the result dict are
+    unchanged. ValueError without ``batched``, for a ``mesh`` that is not a tensor product, with more than one rank,
+    with ``_runner``, or on a mesh ``Problem.batch_ok`` refuses.
     """
     data = np.asarray(data, dtype=np.float64)
     if data.ndim == 1:
@@ -184,6 +190,13 @@ def mbs_impl(data, y, m, mesh=None, n_lambda=100, ftrue=None, lambdas=None, fold
 
     if batched and _runner is not None:
         raise ValueError("batched=True runs the library's own paths; _runner cannot replace them")
+    if device_cv:
+        if not batched:
+            raise ValueError("device_cv=True is a mode of batched=True")
+        if AXES is None:
+            raise ValueError("device_cv=True needs a tensor-product mesh (create_mesh's layout)")
+        if world > 1:
+            raise ValueError("device_cv=True runs every member on one GPU: one rank only")
     if lambdas is None or _runner is None:
         P, idx_full = problem_for(data, y)
         LAMBDAS = create_lambdas(n_lambda, P, lambdas)
@@ -219,7 +232,20 @@ def mbs_impl(data, y, m, mesh=None, n_lambda=100, ftrue=None, lambdas=None, fold
     mse_mat = np.zeros((nl, max(folds, 1)))
     final = None
 
-    if batched:
+    if batched and device_cv:
+        if not P.batch_ok():
+            P.close()
+            raise ValueError(f"batched=True needs a mesh of at most 4096 nodes (p = 4: 1296), got m = {m}")
+        if batch_cosine:
+            P.batch_cosine(batch_cosine)
+        th0 = [y.mean()] + ([y[foldinds != f].mean() for f in range(folds)] if folds > 1 else [])
+        res = P.cv_batch(AXES, data, y, LAMBDAS, fold=foldinds, folds=folds, ref=FTRUE if folds == 1 else y, theta0=th0)
+        mse_mat[:, :] = res["mse_mat"]
+        thetas = list(res["thetas"])
+        final = dict(thetas=thetas, fitted=[th[res["mesh_index"]] for th in thetas], stats=res["stats"][0],
+                     model_mses=res["model_mses"])
+        concurrent = 1
+    elif batched:
         if not P.batch_ok():
             P.close()
             raise ValueError(f"batched=True needs a mesh of at most 4096 nodes (p = 4: 1296), got m = {m}")

@@ -14,6 +14,14 @@ where their theta-solve stops elsewhere (pcg_rtol 1e-10, spectral preconditioner
 The legs batched_cos1 / batched_cos2 are batched=True with batch_cosine=1 / 2 (the in-workgroup cosine theta-solve,
 mvtv_problem_batch_cosine); each batched leg's line carries its own mean PCG iterations per theta-solve.
 
+The leg device_cv is batched=True with device_cv=True: the paths and the fold-MSE matrix through one Problem.cv_batch call
+(mvtv_cv_batch: member setup and scoring on the GPU; profiles/cv_batch/). Every leg's untimed warm-up
+call (three lambdas) is reported too, as `warmup` lines: the first call of a leg pays for the kernels' loading.
+
+    python tools/small_batch_bench.py folds --m 20 --n 100 --fold-list 5 20 0 --legs batched device_cv
+
+folds: the cv mode once per fold count of --fold-list (0: leave-one-out, folds = n), same legs, same method.
+
 sweep: nbatch in --nbatch independent fits at one lambda (own data per member, cold start) through one
 Problem.path_batch call, against the same fits through Problem.admm one after another (the parent path; at most
 --seq-cap of them are run and the per-fit time is reported, so `seq_seconds` of a larger nbatch is that times nbatch).
@@ -58,10 +66,11 @@ def members_of(x, y, m, folds, seed):
     return P, out
 
 
-def run_cv(a):
+def run_cv(a, folds=None):
+    folds = a.folds if folds is None else folds
     m, p = list(a.m), len(a.m)
     x, y = scattered(a.n, p, a.seed)
-    P, mem = members_of(x, y, m, a.folds, 0)
+    P, mem = members_of(x, y, m, folds, 0)
     P.set_data(mem[0][0], mem[0][1])
     lams = cv.create_lambdas(a.n_lambda, P)
     N = P.N
@@ -70,10 +79,11 @@ def run_cv(a):
                                      want_thetas=False)
     iters = sum(s["iters"] for row in stats for s in row)
     pcg = sum(s["pcg_iters"] for row in stats for s in row)
-    base = dict(mode="cv", m=m, n=a.n, folds=a.folds, n_lambda=a.n_lambda, admm_iters=iters,
+    base = dict(mode="cv", m=m, n=a.n, folds=folds, n_lambda=a.n_lambda, admm_iters=iters,
                 pcg_per_solve=pcg / max(iters, 1), maxiter_hits=sum(s["status"] == 1 for row in stats for s in row))
     legs = {"unbatched": {}, "concurrent4": dict(concurrent=4), "batched": dict(batched=True),
-            "batched_cos1": dict(batched=True, batch_cosine=1), "batched_cos2": dict(batched=True, batch_cosine=2)}
+            "batched_cos1": dict(batched=True, batch_cosine=1), "batched_cos2": dict(batched=True, batch_cosine=2),
+            "device_cv": dict(batched=True, device_cv=True)}
     legs = {k: v for k, v in legs.items() if k in a.legs}
     leg_pcg = {}
     for leg, kw in legs.items():   # the cosine legs' own counts, untimed
@@ -86,11 +96,14 @@ def run_cv(a):
                                 pcg_per_solve=sum(s["pcg_iters"] for row in st for s in row) / max(iters, 1))
     P.close()
     for leg, kw in legs.items():   # warm-up: kernels loaded, allocator warm
-        cv.mbs_impl(x, y, m, lambdas=lams[:3], folds=a.folds, group=False, **kw)
+        t0 = time.perf_counter()
+        cv.mbs_impl(x, y, m, lambdas=lams[:3], folds=folds, group=False, **kw)
+        print(json.dumps(dict(mode="cv", warmup=True, m=m, n=a.n, folds=folds, n_lambda=3, leg=leg,
+                              seconds=time.perf_counter() - t0)), flush=True)
     for rep in range(a.repeats):
         for leg, kw in legs.items():
             t0 = time.perf_counter()
-            out = cv.mbs_impl(x, y, m, lambdas=lams, folds=a.folds, group=False, **kw)
+            out = cv.mbs_impl(x, y, m, lambdas=lams, folds=folds, group=False, **kw)
             dt = time.perf_counter() - t0
             print(json.dumps(dict(base, **leg_pcg.get(leg, {}), leg=leg, rep=rep, seconds=dt, its_per_s=iters / dt,
                                   best=out["lambda_minmse_ind"])), flush=True)
@@ -150,10 +163,11 @@ def run_sweep(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=["cv", "sweep"])
+    ap.add_argument("mode", choices=["cv", "folds", "sweep"])
     ap.add_argument("--m", type=int, nargs="+", required=True)
     ap.add_argument("--n", type=int, required=True)
     ap.add_argument("--folds", type=int, default=5)
+    ap.add_argument("--fold-list", type=int, nargs="+", default=[5, 20, 0])
     ap.add_argument("--n-lambda", type=int, default=100)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--seed", type=int, default=0)
@@ -164,7 +178,11 @@ def main():
     ap.add_argument("--cos-modes", type=int, nargs="+", default=[0], choices=[0, 1, 2])
     ap.add_argument("--identity", action="store_true")
     a = ap.parse_args()
-    (run_cv if a.mode == "cv" else run_sweep)(a)
+    if a.mode == "folds":
+        for f in a.fold_list:
+            run_cv(a, a.n if f == 0 else f)
+    else:
+        (run_cv if a.mode == "cv" else run_sweep)(a)
 
 
 if __name__ == "__main__":
