@@ -1,13 +1,8 @@
-// mvtv_capi.cpp — host driver of the ADMM hot path and the C ABI declared in include/mvtv/mvtv.h.
+// mvtv_capi.cpp — the C ABI declared in include/mvtv/mvtv.h, apart from the ADMM loop (mvtv_admm.cpp) and the slab
+// loop (mvtv_slab.cpp): problem set-up, the theta-solves, operators, batch calls, instrumentation.
 //
-// One mvtv_problem = one GPU, one HIP stream, all vectors resident in HBM. The ADMM loop
-// follows the reference variants line by line at the level of scalars (adapt_step, stopping
-// tests, counters); every vector operation is a kernel from mvtv_kernels.hip:
-//   B  rcpp-code/MultivarTV/src/solvers.cpp:96-136   (admm_update, adapt_step :77-94)
-//   A  cpp-code/solvers.cpp:90-130                    (admm_update, adapt_step :70-88)
-//   C  code/solvers.py:53-76                          (mbs_one's loop)
-// Per ADMM iteration the host reads back 7 scalars (one stream sync); the PCG theta-solve
-// keeps its scalars on the device and is polled every few iterations.
+// One mvtv_problem = one GPU, one HIP stream, all vectors resident in HBM; every vector operation is a kernel
+// from the .hip files. The PCG theta-solve keeps its scalars on the device and is polled every few iterations.
 #include <cxxabi.h>
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -74,107 +69,10 @@ std::string kernel_display_name(const void* fn) {
     return s;
 }
 
-// Placement-aware z ping-pong: the fused 3-D kernel's time depends on WHICH physical
-// edge buffer it reads z from and writes to (profiles/r01/v12_zflip_probe.txt: up to 4.70 against
-// 4.15 ms for the two directions of one pair). Once per problem, for 3-D meshes of >= 2^24 nodes, time
-// every ordered pair of four candidate buffers (candidate 0 = edges2, 1..3 = new allocations; `edges`
-// holds the state and is not a candidate) with side-effect-free launches of the steady-state kernel
-// (zeroed z, scratch outputs, no control block), keep the pair with the lowest round-trip cost, move z into
-// it and free the rest. Best effort: any failure (allocation, launch) leaves the allocation-order pair in
-// place, frees everything the probe allocated and clears HIP's error state. MVTV_ZPICK=0 turns it off
-// (MVTV_ZPICK=fail: allocate, then take the failure path; tests/test_gpu_zpick.py).
-// The fused 3-D kernel may skip the twin block (mvtv_internal.h twin_block): one GPU, equal twin weights and state.
-// MVTV_TWIN_OFF=1 (probe builds) keeps both.
-bool twin_ready(const mvtv_problem* P) {
-    if (P->slab || !P->twin_ok || probe_env("MVTV_TWIN_OFF")) return false;
-    if (!((P->g.p == 3 && P->f3d) || (P->g.p == 4 && P->f4d))) return false;
-    return twin_weights_equal(P->g, P->order);
-}
-
-// edge words the twins leave out (the twin blocks' lengths)
-double twin_edges(const mvtv_problem* P) {
-    double t = 0.0;
-    for (int k = 0; k < P->g.nb; ++k)
-        if (twin_of(k, P->g.p, P->order) != k) t += double(P->blk_len[k]);
-    return t;
-}
-
-mvtv_status pick_zpair(mvtv_problem* P, bool track_theta, bool twin) {
-    P->zpicked = true;
-    const char* env = std::getenv("MVTV_ZPICK");
-    if ((env && std::atoi(env) == 0) || P->g.p != 3 || P->g.N < (size_t(1) << 24) || !P->edges2) return MVTV_OK;
-    const size_t ne = size_t(P->g.nb) * P->g.N, bytes = ne * sizeof(double);
-    size_t fr = 0, tot = 0;
-    if (hipMemGetInfo(&fr, &tot) != hipSuccess || fr < 3 * bytes + (size_t(16) << 30)) {
-        (void)hipGetLastError();
-        return MVTV_OK;
-    }
-    constexpr int K = 4, R = 3;
-    double* cand[K] = {P->edges2, nullptr, nullptr, nullptr};
-    double* tmp[3] = {nullptr, nullptr, nullptr};   // the probes' g_alpha / g_u outputs and theta_old input
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    bool ok = true;
-    auto hip = [&](hipError_t e) {
-        if (e != hipSuccess) ok = false;
-        return ok;
-    };
-    for (int i = 1; i < K && ok; ++i) hip(hipMalloc(reinterpret_cast<void**>(&cand[i]), bytes));
-    for (int i = 0; i < 3 && ok; ++i) hip(hipMalloc(reinterpret_cast<void**>(&tmp[i]), size_t(P->g.N) * sizeof(double)));
-    for (int i = 0; i < K && ok; ++i) hip(hipMemsetAsync(cand[i], 0, bytes, P->stream));
-    if (ok) hip(hipMemsetAsync(tmp[2], 0, size_t(P->g.N) * sizeof(double), P->stream));
-    if (ok) hip(hipEventCreate(&ev[0]));
-    if (ok) hip(hipEventCreate(&ev[1]));
-    if (env && std::strcmp(env, "fail") == 0) ok = false;   // test hook: take the failure path after allocating
-    double cost[K][K] = {};
-    for (int rep = 0; rep <= R && ok; ++rep)   // rep 0 warms up
-        for (int i = 0; i < K && ok; ++i)
-            for (int j = 0; j < K && ok; ++j) {
-                if (i == j) continue;
-                int np = 0;
-                float ms = 0.f;
-                if (hip(hipEventRecord(ev[0], P->stream)) &&
-                    hip(launch_admm3d(P->g, P->order, U_FROM_Z, P->stream, P->theta, cand[i], cand[j], 0.0, 1.0, 0.0,
-                                      1.0, track_theta ? tmp[2] : nullptr, tmp[0], tmp[1], P->guprev, P->partials,
-                                      &np, nullptr, false, twin)) &&
-                    hip(hipEventRecord(ev[1], P->stream)) && hip(hipEventSynchronize(ev[1])) &&
-                    hip(hipEventElapsedTime(&ms, ev[0], ev[1])) && rep > 0)
-                    cost[i][j] += ms;
-            }
-    int a = 0, b = 1;
-    if (ok) {
-        for (int i = 0; i < K; ++i)
-            for (int j = i + 1; j < K; ++j)
-                if (cost[i][j] + cost[j][i] < cost[a][b] + cost[b][a]) a = i, b = j;
-        // the probes wrote only the candidates, tmp and the partials (scratch until the next reduction)
-        ok = hip(hipMemcpyAsync(cand[a], P->edges, bytes, hipMemcpyDeviceToDevice, P->stream)) &&
-             hip(hipStreamSynchronize(P->stream));
-    }
-    (void)hipStreamSynchronize(P->stream);
-    for (auto e : ev)
-        if (e) (void)hipEventDestroy(e);
-    for (auto t : tmp)
-        if (t) (void)hipFree(t);
-    if (!ok) {   // keep (edges, edges2); the candidates' contents were never used
-        for (int i = 1; i < K; ++i)
-            if (cand[i]) (void)hipFree(cand[i]);
-        (void)hipGetLastError();
-        return MVTV_OK;
-    }
-    (void)hipFree(P->edges);
-    for (int i = 0; i < K; ++i)
-        if (i != a && i != b) (void)hipFree(cand[i]);
-    P->edges = cand[a];
-    P->edges2 = cand[b];
-    if (probe_env("MVTV_ZPICK_LOG"))
-        std::fprintf(stderr, "[mvtv] z pair %d,%d: %.3f / %.3f ms (candidate 0 = edges2, 1-3 new; pair 0,1: %.3f / %.3f)\n",
-                     a, b, cost[a][b] / R, cost[b][a] / R, cost[0][1] / R, cost[1][0] / R);
-    return MVTV_OK;
-}
-
 void free_all(mvtv_problem* P) {
     double** bufs[] = {&P->oty, &P->wdiag, &P->theta, &P->edges, &P->ga, &P->gu, &P->guprev, &P->r,
                        &P->p, &P->q, &P->thold, &P->p2, &P->partials, &P->red, &P->stage, &P->slab_iface,
-                       &P->edges2, &P->pcg_b, &P->g4, &P->edges3, &P->pcg_s, &P->pcg_t, &P->ls_coef, &P->ls_lr};
+                       &P->edges2, &P->pcg_b, &P->g4, &P->pcg_s, &P->pcg_t, &P->ls_coef, &P->ls_lr};
     for (double** b : bufs)
         if (*b) {
             (void)hipFree(*b);
@@ -201,13 +99,13 @@ void free_all(mvtv_problem* P) {
         (void)hipEventDestroy(pd.b);
     }
     for (auto e : P->ev_pool) (void)hipEventDestroy(e);
-    for (auto& lg : P->graphs)
-        if (lg.exec) (void)hipGraphExecDestroy(lg.exec);
-    P->graphs.clear();
     if (P->stream) (void)hipStreamDestroy(P->stream);
     if (P->comm_stream) (void)hipStreamDestroy(P->comm_stream);
 }
 
+}  // namespace
+// (namespace mvtv, here and below: declared in mvtv_problem.h for the ADMM loop of mvtv_admm.cpp)
+namespace mvtv {
 double variant_tol(const mvtv_admm_opts& o) {
     if (o.tol > 0) return o.tol;
     return o.variant == MVTV_VARIANT_RCPP ? 1e-4 : 1e-3;
@@ -216,6 +114,8 @@ int variant_maxc(const mvtv_admm_opts& o) {
     if (o.max_counter > 0) return o.max_counter;
     return o.variant == MVTV_VARIANT_RCPP ? 3000 : (o.variant == MVTV_VARIANT_CPP ? 2000 : 1000000);
 }
+}  // namespace mvtv
+namespace {
 
 // Copy a compact [E] edge vector (reference block layout) into the padded device layout.
 mvtv_status import_edges(mvtv_problem* P, const double* host_u, double* padded) {
@@ -265,7 +165,9 @@ int pcg_ahead() {
     }();
     return v;
 }
+}  // namespace
 
+namespace mvtv {
 // Solve (W + sigma D^T D) x = b, b = oty + ca*ga + cb*gb, by Jacobi-PCG warm-started at x.
 mvtv_status pcg_solve(mvtv_problem* P, double sigma, const double* oty, const double* ga, double ca,
                       const double* gb, double cb, double* x, double rtol, int maxit, int* iters, double* relres) {
@@ -355,19 +257,9 @@ mvtv_status pcg_solve(mvtv_problem* P, double sigma, const double* oty, const do
 }
 
 bool spectral_ok(const mvtv_problem* P) { return P->spec_mesh && P->wmode == W_IDENTITY; }
+}  // namespace mvtv
 
-// Graph replay of the asynchronous loop: probe builds only (MVTV_ADMM_GRAPH=1). Measured slower than the stream
-// launches it replaces, one process each, event-free (tools/launch_gap_probe.py, profiles/r04/v1_launch_gap):
-// 1024^2 13510 against 14083 ADMM it/s, 2048^2 6088 against 6187. The ~37 us of "gaps" per 1024^2 iteration that
-// the round-3 trace showed were the per-launch timing events (10105 it/s with them).
-bool admm_graph_enabled() {
-    static const bool on = [] {
-        const char* e = probe_env("MVTV_ADMM_GRAPH");
-        return e && std::atoi(e) != 0;
-    }();
-    return on;
-}
-
+namespace {
 // M = 2^ceil(log2(2m - 1)): the circular convolution length of Bluestein's identity for length m
 uint32_t bluestein_length(uint32_t m) {
     uint32_t M = 1;
@@ -772,11 +664,13 @@ mvtv_status dct_split_setup(mvtv_problem* P) {
 
 // a leading dimension runs in two passes (or the chirp transform's three): the passes that hold a whole line of it in
 // one workgroup rest
-bool split_on(const mvtv_problem* P) {
+}  // namespace
+bool mvtv::split_on(const mvtv_problem* P) {
     for (int j = 0; j < P->g.p - 1; ++j)
         if (P->spec.split[j].a > 0 || P->spec.chirp[j].a > 0) return true;
     return false;
 }
+namespace {
 
 // Which meshes the spectral solve takes. Cosine transforms of any length <= 4096: FFT plans for 2-3-5-7 lengths,
 // Bluestein (k_dctb8) for the rest; a longer leading dimension with a factorisation a * b, both 2-3-5-7-smooth and
@@ -816,14 +710,6 @@ mvtv_status spectral_setup(mvtv_problem* P) {
     if (P->spec_long && P->spec.lb.nblk == 0) MVTV_TRY(line_blocks_setup(P, 0));
     if (P->spec_mesh && !P->slab) MVTV_TRY(dct_split_setup(P));
     return MVTV_OK;
-}
-
-// a captured loop (probe builds) holds the launches of the transforms it was captured with: dct_split and dct_chirp
-// change them without changing any buffer of the graph's key
-void drop_graphs(mvtv_problem* P) {
-    for (auto& lg : P->graphs)
-        if (lg.exec) (void)hipGraphExecDestroy(lg.exec);
-    P->graphs.clear();
 }
 
 // a mesh that is refused (again): no transform is in use, and what the spectral period allocated beyond the mesh's
@@ -868,13 +754,16 @@ mvtv_status line_sweeps(mvtv_problem* P, double* x, double sigma, double w0, con
     return MVTV_OK;
 }
 
+}  // namespace
+
+namespace mvtv {
 // Direct solve (I + sigma D^T D) x = oty + ca*ga + cb*gb: forward DCT along dims 0..p-2, the
 // last dim's forward/divide/inverse in one pass, inverse DCT along dims p-2..0. All in place on x.
 // fold: b = oty + fold_ka ga + fold_kb gb from the control block (ga = the fused kernel's folded
 // s = rho (D^T alpha + D^T u), gb = D^T u)
 mvtv_status spectral_solve(mvtv_problem* P, double sigma, const double* oty, const double* ga, double ca,
-                           const double* gb, double cb, double* x, const AdmmCtl* ctl = nullptr, double w0 = 1.0,
-                           const int32_t* skip = nullptr, bool fold = false) {
+                           const double* gb, double cb, double* x, const AdmmCtl* ctl, double w0, const int32_t* skip,
+                           bool fold) {
     const int p = P->g.p;
     // the first pass of a solve, along dim 0 (p = 1: the only one, mode 2): oty into x, b formed on load when ga is
     // given (fold: b = oty + fold_ka s + fold_kb g_u, g_u read after a rho change)
@@ -1071,10 +960,7 @@ mvtv_status ensure_state(mvtv_problem* P) {
     return MVTV_OK;
 }
 
-}  // namespace
-
-// the slab loop's ranks pick their z ping-pong pair the same way (mvtv_slab.cpp)
-mvtv_status zpair_pick(mvtv_problem* P, bool track_theta, bool twin) { return pick_zpair(P, track_theta, twin); }
+}  // namespace mvtv
 
 // =================================================================================== C ABI
 extern "C" {
@@ -1334,7 +1220,6 @@ mvtv_status mvtv_problem_dct_split(mvtv_problem* P, int32_t dim, int32_t a) {
     if (a != 0 && P->chirp_forced[dim][0] != 0)
         return fail(MVTV_BAD_ARG, "dct_split: the dimension is under dct_chirp");
     P->split_forced[dim] = a;
-    drop_graphs(P);
     return dct_split_setup(P);
 }
 
@@ -1360,7 +1245,6 @@ mvtv_status mvtv_problem_dct_chirp(mvtv_problem* P, int32_t dim, int32_t a, int3
     const int32_t old_a = P->chirp_forced[dim][0], old_b = P->chirp_forced[dim][1];
     P->chirp_forced[dim][0] = a;
     P->chirp_forced[dim][1] = b;
-    drop_graphs(P);
     const mvtv_status s = chirp_apply(P);
     if (s != MVTV_OK) {   // e.g. no memory for the ~2N scratch: back to the mode before the call
         P->chirp_forced[dim][0] = old_a;
@@ -1460,528 +1344,6 @@ mvtv_status mvtv_state_get(mvtv_problem* P, double* theta, double* u, double* rh
     }
     if (rho) *rho = P->rho;
     return MVTV_OK;
-}
-
-mvtv_status mvtv_admm_run(mvtv_problem* P, const mvtv_admm_opts* opts_in, double lambda, mvtv_admm_stats* stats) {
-    if (!P || !opts_in) return fail(MVTV_BAD_ARG, "null problem/opts");
-    MVTV_TRY(ensure_state(P));
-    if (!(lambda >= 0.0)) return fail(MVTV_BAD_ARG, "lambda must be >= 0");
-    const auto t0 = std::chrono::steady_clock::now();
-    DeviceGuard dg(P->device);
-    const mvtv_admm_opts& o = *opts_in;
-    const int variant = o.variant;
-    if (variant < 0 || variant > 2) return fail(MVTV_BAD_ARG, "variant");
-    const double tol = variant_tol(o);
-    const int max_counter = variant_maxc(o);
-    const double rtol = o.pcg_rtol > 0 ? o.pcg_rtol : 1e-10;
-    const int pcg_maxit = o.pcg_max_iter > 0 ? o.pcg_max_iter : 20000;
-    const Launch L = P->L();
-    const double N = double(P->g.N), E = double(P->E);
-    if (o.theta_solver < MVTV_SOLVER_AUTO || o.theta_solver > MVTV_SOLVER_PCG_SPECTRAL)
-        return fail(MVTV_BAD_ARG, "theta_solver");
-    if (o.theta_solver == MVTV_SOLVER_SPECTRAL && !spectral_ok(P))
-        return fail(MVTV_BAD_ARG, "spectral theta-solve needs W = I and every m_j, j < p - 1, <= 4096 or a product of two 2-3-5-7-smooth factors <= 4096");
-    if (o.theta_solver == MVTV_SOLVER_PCG_SPECTRAL && (!P->spec_mesh || P->wmode == W_NONE))
-        return fail(MVTV_BAD_ARG, "spectral preconditioner needs every m_j, j < p - 1, <= 4096 or a product of two 2-3-5-7-smooth factors <= 4096");
-    const bool spectral = o.theta_solver == MVTV_SOLVER_SPECTRAL ||
-                          (o.theta_solver == MVTV_SOLVER_AUTO && spectral_ok(P));
-    // AUTO with W != I on a spectral mesh: PCG with the spectral preconditioner (K an order of magnitude
-    // below Jacobi's once sigma D^T D dominates); other meshes: Jacobi-PCG
-    const bool pcg_spec = o.theta_solver == MVTV_SOLVER_PCG_SPECTRAL ||
-                          (o.theta_solver == MVTV_SOLVER_AUTO && !spectral && P->spec_mesh && P->wmode != W_NONE &&
-                           !P->slab);
-
-    // ---- initial state: u explicit in the edge buffer, alpha_0 = D theta_0 ------------------
-    double rho;
-    if (variant == MVTV_VARIANT_RCPP) rho = P->rho;                      // rho_init (:100)
-    else if (variant == MVTV_VARIANT_CPP) rho = double(int(lambda));     // int rho = lambda (:108)
-    else rho = lambda;                                                   // rho = tune (py :55)
-    double sigma = std::isnan(o.sigma) ? (variant == MVTV_VARIANT_RCPP ? rho : lambda) : o.sigma;
-    double* gprev = P->guprev;
-    double* gnew = P->gu;
-    double c_prev = 1.0, t_z = 0.0;
-    int mode = U_EXPLICIT;
-    int h = -1;
-    if (P->edge_mode == U_FROM_Z) {
-        // resume from the resident state of the previous call: u0 = -c clamp(z, t_z) is read straight
-        // from z by the first edge update, and P->guprev already holds D^T clamp-part of it (scale c)
-        mode = U_FROM_Z;
-        t_z = P->t_z;
-        c_prev = P->c_state;
-    } else {
-        if (P->u_default) {
-            const double u0 = variant == MVTV_VARIANT_RCPP ? 0.0 : 1.0 / lambda;   // A :101, C :62
-            HIP_TRY(launch_edges_fill_valid(P->g, P->order, L, P->edges, u0));
-            P->u_default = false;
-        }
-        // g_uprev = D^T u0
-        h = P->tstart(MVTV_K_GATHER);
-        int np0 = L.grid;
-        if (P->e3d)
-            HIP_TRY(launch_gather3d(P->g, P->order, U_EXPLICIT, P->stream, P->edges, 0.0, nullptr, gprev, nullptr, 1.0,
-                                    P->partials, &np0, nullptr, P->g4));
-        else
-            HIP_TRY(launch_gather(P->g, P->order, U_EXPLICIT, L, P->edges, 0.0, nullptr, gprev, nullptr, 1.0,
-                                  P->partials));
-        P->tstop(h);
-    }
-    // g_alpha = D^T D theta0 (alpha0 = D theta0, rcpp…/solvers.cpp:101)  ->  b_1 = oty + rho D^T (alpha0 + u0)
-    h = P->tstart(MVTV_K_OTHER);
-    HIP_TRY(launch_apply_A(P->g, L, 1.0, W_NONE, nullptr, P->theta, P->ga, nullptr, nullptr));
-    P->tstop(h);
-    int np = L.grid;
-
-    const bool track_theta = variant != MVTV_VARIANT_RCPP;
-    const bool fused = P->f3d;
-    const bool fused4 = P->f4d;   // 4-D: edge update + gather pass A fused, pass B separate
-    const bool pingpong = fused || fused4;
-    if (pingpong && !P->edges2) MVTV_TRY(alloc(&P->edges2, size_t(P->g.nb) * P->g.N));
-    // MVTV_EBUF3=1: z rotates over three buffers (when the third fits with 16 GiB to spare). Opt-in:
-    // over five boxes it is as often slower as faster than two (profiles/r01/v8_ebuf3_ab.txt)
-    static const int rot3_env = [] {
-        const char* e = probe_env("MVTV_EBUF3");
-        return e ? std::atoi(e) : 0;
-    }();
-    if (fused && spectral && rot3_env != 0 && !P->edges3) {
-        const size_t ne = size_t(P->g.nb) * P->g.N;
-        size_t fr = 0, tot = 0;
-        const bool fits = hipMemGetInfo(&fr, &tot) == hipSuccess && fr > ne * sizeof(double) + (size_t(16) << 30);
-        if (rot3_env > 0 || fits) MVTV_TRY(alloc(&P->edges3, ne));
-    }
-    const int nbuf = (fused && P->edges3) ? 3 : 2;
-    // MVTV_ZFLIP (probe only, tools/zflip_probe.py): move z to the other edge buffer before this run,
-    // so the g_u ping-pong meets the z ping-pong in the other pairing of physical buffers
-    if (fused && nbuf == 2 && probe_env("MVTV_ZFLIP")) {
-        HIP_TRY(hipMemcpyAsync(P->edges2, P->edges, size_t(P->g.nb) * P->g.N * sizeof(double),
-                               hipMemcpyDeviceToDevice, P->stream));
-        std::swap(P->edges, P->edges2);
-    }
-    if (fused && probe_env("MVTV_GFLIP")) {   // probe only: the same for the g_u ping-pong
-        HIP_TRY(hipMemcpyAsync(P->gu, P->guprev, size_t(P->g.N) * sizeof(double), hipMemcpyDeviceToDevice,
-                               P->stream));
-        std::swap(P->gu, P->guprev);
-    }
-    // the twin blocks are skipped by the fused kernels and filled from their group's first block when the run ends
-    const bool twin = (fused || fused4) && twin_ready(P);
-    // an early return (MVTV_TRY / HIP_TRY) after twin-skipping iterations must not leave a stale twin block behind
-    // twin_ok: fill the twins of both edge buffers (whichever holds the state), best effort; the normal exits
-    // fill them themselves and disarm
-    struct TwinGuard {
-        mvtv_problem* P;
-        bool armed;
-        ~TwinGuard() {
-            if (!armed) return;
-            (void)fill_twins(P->g, P->order, P->stream, P->edges);
-            if (P->edges2) (void)fill_twins(P->g, P->order, P->stream, P->edges2);
-            if (P->edges3) (void)fill_twins(P->g, P->order, P->stream, P->edges3);
-            (void)hipStreamSynchronize(P->stream);
-            (void)hipGetLastError();
-        }
-    } twin_guard{P, twin};
-    if (P->timing && (fused || fused4)) P->twin_timed = twin;
-    if (fused && spectral && nbuf == 2 && !P->zpicked) MVTV_TRY(pick_zpair(P, track_theta, twin));
-    double dtheta = 0.0;
-    if (track_theta) {
-        if (!P->thold) MVTV_TRY(alloc(&P->thold, P->g.N));
-        HIP_TRY(launch_fill(P->stream, P->thold, o.ymean - (variant == MVTV_VARIANT_CPP ? 0.1 : 1.0), P->g.N));
-        HIP_TRY(launch_maxabsdiff(P->g, L, P->theta, P->thold, P->partials));
-        HIP_TRY(launch_finalize(P->stream, P->partials, L.grid, 1, 1, 0, P->red, P->st));
-        HIP_TRY(hipMemcpyAsync(P->host_red, P->red, sizeof(double), hipMemcpyDeviceToHost, P->stream));
-        MVTV_TRY(P->sync());
-        dtheta = P->host_red[0];
-    }
-
-    // ---- asynchronous loop (spectral theta-solve): the decisions of every iteration are taken on
-    // the device by k_admm_control, the host enqueues iterations ahead and polls the done flag -------
-    const bool first_runs = o.fixed_iters > 0 ? o.fixed_iters > 0
-                                              : (variant == MVTV_VARIANT_RCPP ? true
-                                                                              : (dtheta > tol && !(variant == MVTV_VARIANT_PY &&
-                                                                                                   max_counter <= 0)));
-    if (spectral && first_runs && !std::getenv("MVTV_ADMM_SYNC")) {
-        AdmmCtl& c = *P->host_ctl;
-        std::memset(&c, 0, sizeof(c));
-        c.variant = variant;
-        c.fixed_iters = o.fixed_iters > 0 ? o.fixed_iters : 0;
-        c.max_counter = max_counter;
-        c.lambda = lambda;
-        c.tol = tol;
-        c.sqrtN = std::sqrt(N);
-        c.sqrtE = std::sqrt(E);
-        c.rho = rho;
-        c.sigma = sigma;
-        c.c_prev = c_prev;
-        c.t_z = t_z;
-        c.t_next = rho != 0.0 ? lambda / rho : INFINITY;
-        c.counter = 1;
-        c.dtheta = dtheta;
-        c.dual_norm = c.primal_norm = 1.0;
-        c.eps_dual = c.eps_pri = tol;
-        HIP_TRY(hipMemcpyAsync(P->ctl, &c, sizeof(AdmmCtl), hipMemcpyHostToDevice, P->stream));
-        double* gbuf[2] = {P->guprev, P->gu};
-        double* ebuf[3] = {P->edges, P->edges2, P->edges3};
-        // FOLD (variant B): the fused 3-D kernel stores s = rho (D^T alpha + D^T u) in P->ga instead of D^T alpha, so
-        // the next solve's first pass reads oty and s (2N words) instead of oty, D^T alpha and D^T u (3N); after a
-        // control step that changed rho it forms oty + (rho'/rho) s + rho' (c - 1) D^T u (AdmmCtl::fold_ka / _kb)
-        // (the first pass transforms dim 0)
-        const uint32_t m0 = P->g.m[0];
-        const bool fold_path = fused ? (P->g.p == 2 || P->g.p == 3)
-                                     : (P->g.p == 4 && P->e3d && P->g4 != nullptr && gather4_ok(P->g));   // two-pass 4-D
-        const bool fold = fold_path && variant == MVTV_VARIANT_RCPP && m0 >= 8 && m0 <= 4096 &&
-                          (m0 & (m0 - 1)) == 0 && !split_on(P) && !probe_env("MVTV_FOLD_OFF") &&
-                          !probe_env("MVTV_DCT_LDS");
-        auto enqueue = [&](int j) -> mvtv_status {
-            double* gp = gbuf[j & 1];
-            double* gn = gbuf[(j + 1) & 1];
-            const int um = j == 0 ? mode : U_FROM_Z;
-            if (track_theta)
-                HIP_TRY(hipMemcpyAsync(P->thold, P->theta, size_t(P->g.N) * sizeof(double), hipMemcpyDeviceToDevice,
-                                       P->stream));
-            MVTV_TRY(spectral_solve(P, sigma, P->oty, P->ga, rho, gp, rho, P->theta, P->ctl, 1.0, nullptr,
-                                    fold && j > 0));
-            if (fused) {   // z ping-pongs between the two edge buffers
-                int hh = P->tstart(MVTV_K_ADMM_FUSED);
-                int npf = 0;
-                HIP_TRY(launch_admm3d(P->g, P->order, um, P->stream, P->theta, ebuf[j % nbuf], ebuf[(j + 1) % nbuf], 0.0, 1.0,
-                                      0.0, 1.0, track_theta ? P->thold : nullptr, P->ga, gn, gp, P->partials, &npf,
-                                      P->ctl, fold, twin));
-                P->tstop(hh);
-                hh = P->tstart(MVTV_K_REDUCE);
-                HIP_TRY(launch_finalize(P->stream, P->partials, npf, ER_N + GR_N, -(1 << ER_DTH), 0, P->red, P->st, 0.0,
-                                        0, P->ctl, P->ctl, P->red));   // + the control step
-                P->tstop(hh);
-                return MVTV_OK;
-            }
-            if (fused4) {   // z ping-pongs as in the 3-D fused loop; pass B of the gather after the ER reduction
-                int hh = P->tstart(MVTV_K_ADMM_FUSED4);
-                int npe = 0;
-                HIP_TRY(launch_admm4a(P->g, P->order, um, P->stream, P->theta, ebuf[j % nbuf], ebuf[(j + 1) % nbuf], 0.0,
-                                      1.0, 0.0, track_theta ? P->thold : nullptr, P->g4, P->partials, &npe, P->ctl,
-                                      twin));
-                P->tstop(hh);
-                hh = P->tstart(MVTV_K_REDUCE);
-                HIP_TRY(launch_finalize(P->stream, P->partials, npe, ER_N, 1, 0, P->red, P->st, 0.0, 0, P->ctl));
-                P->tstop(hh);
-                hh = P->tstart(MVTV_K_GATHER4B);
-                int npg = 0;
-                HIP_TRY(launch_gather4b(P->g, U_FROM_Z, P->stream, P->ga, gn, gp, 1.0, P->partials, &npg, P->ctl, P->g4,
-                                        fold));
-                P->tstop(hh);
-                hh = P->tstart(MVTV_K_REDUCE);
-                HIP_TRY(launch_finalize(P->stream, P->partials, npg, GR_N, 0, 0, P->red + ER_N, P->st, 0.0, 0, P->ctl,
-                                        P->ctl, P->red));   // + the control step
-                P->tstop(hh);
-                return MVTV_OK;
-            }
-            int hh = P->tstart(MVTV_K_EDGE_UPDATE);
-            int npe = L.grid;
-            if (P->e3d)
-                HIP_TRY(launch_edge3d(P->g, P->order, um, P->stream, P->theta, P->edges, 0.0, 1.0, 0.0,
-                                      track_theta ? P->thold : nullptr, P->partials, &npe, P->ctl));
-            else
-                HIP_TRY(launch_edge_update(P->g, P->order, um, L, P->theta, P->edges, 0.0, 1.0, 0.0,
-                                           track_theta ? P->thold : nullptr, P->partials, P->ctl));
-            P->tstop(hh);
-            hh = P->tstart(MVTV_K_REDUCE);
-            HIP_TRY(launch_finalize(P->stream, P->partials, npe, ER_N, 1, 0, P->red, P->st, 0.0, 0, P->ctl));
-            P->tstop(hh);
-            hh = P->tstart(MVTV_K_GATHER);
-            const int hb = P->tstart_b(MVTV_K_GATHER4B);
-            int npg = L.grid;
-            if (P->e3d)
-                HIP_TRY(launch_gather3d(P->g, P->order, U_FROM_Z, P->stream, P->edges, 0.0, P->ga, gn, gp, 1.0,
-                                        P->partials, &npg, P->ctl, P->g4, fold));
-            else
-                HIP_TRY(launch_gather(P->g, P->order, U_FROM_Z, L, P->edges, 0.0, P->ga, gn, gp, 1.0, P->partials,
-                                      P->ctl));
-            P->tstop(hh);
-            P->tstop_b(hb);
-            hh = P->tstart(MVTV_K_REDUCE);
-            HIP_TRY(launch_finalize(P->stream, P->partials, npg, GR_N, 0, 0, P->red + ER_N, P->st, 0.0, 0, P->ctl, P->ctl,
-                                    P->red));   // + the control step
-            P->tstop(hh);
-            return MVTV_OK;
-        };
-        const int limit = o.fixed_iters > 0 ? o.fixed_iters
-                                            : (variant == MVTV_VARIANT_PY ? max_counter : max_counter + 1);
-        int target = o.fixed_iters > 0 ? o.fixed_iters : (P->admm_hint > 0 ? P->admm_hint : 16);
-        // Iterations j >= 1 repeat with period 2 (the z and D^T u ping-pongs), so iterations (odd j, j + 1) can be
-        // replayed as one captured HIP graph instead of ~10 stream launches: without per-launch events, for meshes
-        // whose launches are short enough for the launch path to matter (< 2^24 nodes)
-        hipGraphExec_t gexec = nullptr;
-        if (!P->timing && nbuf == 2 && P->g.N < (uint32_t(1) << 24) && admm_graph_enabled()) {
-            const std::vector<const void*> key = {P->theta, P->oty, P->ga, P->thold, gbuf[0], gbuf[1], ebuf[0], ebuf[1],
-                                                  reinterpret_cast<const void*>(uintptr_t(fold)),
-                                                  reinterpret_cast<const void*>(uintptr_t(track_theta)),
-                                                  reinterpret_cast<const void*>(uintptr_t(fused)),
-                                                  reinterpret_cast<const void*>(uintptr_t(twin)), P->ls_coef,
-                                                  reinterpret_cast<const void*>(uintptr_t(P->ls_chunks)), P->spec.lb_coef,
-                                                  reinterpret_cast<const void*>(uintptr_t(P->spec.lb.nblk))};
-            auto it = std::find_if(P->graphs.begin(), P->graphs.end(), [&](const auto& lg) { return lg.key == key; });
-            if (it == P->graphs.end()) {
-                // capture iterations 1 and 2; any failure leaves stream launches for this key (best effort)
-                mvtv_problem::LoopGraph lg;
-                lg.key = key;
-                hipGraph_t gr = nullptr;
-                if (hipStreamBeginCapture(P->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                    const bool ok = enqueue(1) == MVTV_OK && enqueue(2) == MVTV_OK;
-                    const bool ended = hipStreamEndCapture(P->stream, &gr) == hipSuccess;
-                    if (ok && ended && gr && hipGraphInstantiate(&lg.exec, gr, nullptr, nullptr, 0) != hipSuccess)
-                        lg.exec = nullptr;
-                    if (gr) (void)hipGraphDestroy(gr);
-                }
-                (void)hipGetLastError();
-                if (P->graphs.size() >= 4) {   // the two z / D^T u parities of a few buffer sets
-                    if (P->graphs.front().exec) (void)hipGraphExecDestroy(P->graphs.front().exec);
-                    P->graphs.erase(P->graphs.begin());
-                }
-                P->graphs.push_back(lg);
-                it = P->graphs.end() - 1;
-            }
-            gexec = it->exec;
-        }
-        const bool use_graph = gexec != nullptr;
-        std::vector<size_t> mark;   // first timing entry of each enqueued iteration
-        int enq = 0;
-        for (;;) {
-            while (enq < target && enq < limit) {
-                if (use_graph && (enq & 1) && enq + 2 <= std::min(target, limit)) {
-                    HIP_TRY(hipGraphLaunch(gexec, P->stream));
-                    enq += 2;
-                    continue;
-                }
-                mark.push_back(P->pending.size());
-                MVTV_TRY(enqueue(enq++));
-            }
-            HIP_TRY(hipMemcpyAsync(P->host_ctl, P->ctl, sizeof(AdmmCtl), hipMemcpyDeviceToHost, P->stream));
-            HIP_TRY(hipStreamSynchronize(P->stream));
-            if (c.done || enq >= limit) break;
-            target = enq + std::max(4, enq / 4);
-        }
-        const int it_done = c.it;
-        if (P->timing && it_done < int(mark.size()))   // iterations enqueued past the stop did no work
-            for (size_t e = mark[size_t(it_done)]; e < P->pending.size(); ++e) P->pending[e].kid = -1;
-        P->harvest();
-        if (P->timing && fold) P->fold_fix += c.nfix;
-        if (o.fixed_iters <= 0 && c.status == 0) P->admm_hint = it_done + 1;
-        if (it_done & 1) std::swap(P->guprev, P->gu);   // P->guprev holds D^T u of the current state
-        if (fused && nbuf == 3) {   // the state is in ebuf[it_done % 3]
-            P->edges = ebuf[it_done % 3];
-            P->edges2 = ebuf[(it_done + 1) % 3];
-            P->edges3 = ebuf[(it_done + 2) % 3];
-        } else if (pingpong && (it_done & 1)) {
-            std::swap(P->edges, P->edges2);
-        }
-        twin_guard.armed = false;
-        if (twin) HIP_TRY(fill_twins(P->g, P->order, P->stream, P->edges));
-        if (it_done > 0) P->edge_mode = U_FROM_Z;
-        if (it_done > 0) P->t_z = c.t_z;
-        P->c_state = c.c_prev;
-        P->rho = c.rho;
-        mvtv_admm_stats S{};
-        S.iters = it_done;
-        S.rho = c.rho;
-        S.r_norm = c.r_norm;
-        S.s_norm = c.s_norm;
-        if (variant == MVTV_VARIANT_RCPP) {
-            S.eps_pri = c.eps_pri;
-            S.eps_dual = c.eps_dual;
-        }
-        S.dtheta_max = c.dtheta;
-        S.theta_solver = MVTV_SOLVER_SPECTRAL;
-        mvtv_status status = c.status ? MVTV_MAXITER : MVTV_OK;
-        if (status == MVTV_MAXITER) {
-            if (variant == MVTV_VARIANT_CPP) fail(status, "Failed to converge!");
-            else if (variant == MVTV_VARIANT_RCPP && o.verbose) std::printf("ADMM reached max_counter at lambda = %g\n", lambda);
-        }
-        if (o.verbose) std::printf("Lambda= %g, Counter = %d\n", lambda, c.counter);
-        S.status = status;
-        S.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        if (stats) *stats = S;
-        return status;
-    }
-
-    mvtv_admm_stats S{};
-    S.status = MVTV_OK;
-    double dual_norm = 1.0, primal_norm = 1.0, eps_dual = tol, eps_primal = tol;
-    int counter = 1, it = 0;
-    mvtv_status status = MVTV_OK;
-    for (;;) {
-        // ---- loop condition, evaluated at the top as in the reference -----------------------
-        if (o.fixed_iters > 0) {
-            if (it >= o.fixed_iters) break;
-        } else if (variant == MVTV_VARIANT_RCPP) {
-            if (!(dual_norm > eps_dual || primal_norm > eps_primal)) break;   // :110
-        } else {
-            if (!(dtheta > tol)) break;   // any(|theta - thetaold| > TOL): A :113, C :69
-            if (variant == MVTV_VARIANT_PY && it >= max_counter) {
-                status = MVTV_MAXITER;
-                break;
-            }
-        }
-        if (track_theta) HIP_TRY(hipMemcpyAsync(P->thold, P->theta, size_t(P->g.N) * sizeof(double),
-                                                hipMemcpyDeviceToDevice, P->stream));
-        // ---- theta-update: (W + sigma D^T D) theta = oty + rho D^T (alpha + u) ----------------
-        int pit = 0;
-        double relres = 0.0;
-        if (spectral)
-            MVTV_TRY(spectral_solve(P, sigma, P->oty, P->ga, rho, gprev, rho * c_prev, P->theta));
-        else if (pcg_spec)
-            MVTV_TRY(pcgs_solve(P, sigma, P->oty, P->ga, rho, gprev, rho * c_prev, P->theta, rtol, pcg_maxit, &pit,
-                                &relres));
-        else
-            MVTV_TRY(pcg_solve(P, sigma, P->oty, P->ga, rho, gprev, rho * c_prev, P->theta, rtol, pcg_maxit, &pit,
-                               &relres));
-        S.pcg_iters += pit;
-        S.pcg_iters_max = std::max(S.pcg_iters_max, pit);
-        if (!spectral && pit >= pcg_maxit && !(relres <= rtol)) {
-            S.pcg_unconverged += 1;
-            if (o.pcg_strict) {
-                status = MVTV_PCG_NOT_CONVERGED;
-                fail(status, "PCG hit pcg_max_iter");
-                break;
-            }
-        }
-        // ---- z-update (soft threshold) and dual update over all edges -----------------------
-        const double t_new = rho != 0.0 ? lambda / rho : INFINITY;
-        if (fused) {   // edge update + gather in one pass, z ping-pongs between the edge buffers
-            h = P->tstart(MVTV_K_ADMM_FUSED);
-            HIP_TRY(launch_admm3d(P->g, P->order, mode, P->stream, P->theta, P->edges, P->edges2, t_z, c_prev, t_new,
-                                  c_prev, track_theta ? P->thold : nullptr, P->ga, gnew, gprev, P->partials, &np,
-                                  nullptr, false, twin));
-            P->tstop(h);
-            std::swap(P->edges, P->edges2);
-            h = P->tstart(MVTV_K_REDUCE);
-            HIP_TRY(launch_finalize(P->stream, P->partials, np, ER_N + GR_N, -(1 << ER_DTH), 0, P->red, P->st));
-            P->tstop(h);
-            mode = U_FROM_Z;
-            t_z = t_new;
-        } else if (fused4) {   // 4-D: edge update + gather pass A in one pass (z ping-pong), then pass B
-            h = P->tstart(MVTV_K_ADMM_FUSED4);
-            HIP_TRY(launch_admm4a(P->g, P->order, mode, P->stream, P->theta, P->edges, P->edges2, t_z, c_prev, t_new,
-                                  track_theta ? P->thold : nullptr, P->g4, P->partials, &np, nullptr, twin));
-            P->tstop(h);
-            std::swap(P->edges, P->edges2);
-            h = P->tstart(MVTV_K_REDUCE);
-            HIP_TRY(launch_finalize(P->stream, P->partials, np, ER_N, 1, 0, P->red, P->st));
-            P->tstop(h);
-            mode = U_FROM_Z;
-            t_z = t_new;
-            h = P->tstart(MVTV_K_GATHER4B);
-            HIP_TRY(launch_gather4b(P->g, U_FROM_Z, P->stream, P->ga, gnew, gprev, c_prev, P->partials, &np, nullptr,
-                                    P->g4));
-            P->tstop(h);
-            h = P->tstart(MVTV_K_REDUCE);
-            HIP_TRY(launch_finalize(P->stream, P->partials, np, GR_N, 0, 0, P->red + ER_N, P->st));
-            P->tstop(h);
-        } else {
-            h = P->tstart(MVTV_K_EDGE_UPDATE);
-            np = L.grid;
-            if (P->e3d)
-                HIP_TRY(launch_edge3d(P->g, P->order, mode, P->stream, P->theta, P->edges, t_z, c_prev, t_new,
-                                      track_theta ? P->thold : nullptr, P->partials, &np));
-            else
-                HIP_TRY(launch_edge_update(P->g, P->order, mode, L, P->theta, P->edges, t_z, c_prev, t_new,
-                                           track_theta ? P->thold : nullptr, P->partials));
-            P->tstop(h);
-            h = P->tstart(MVTV_K_REDUCE);
-            HIP_TRY(launch_finalize(P->stream, P->partials, np, ER_N, 1, 0, P->red, P->st));
-            P->tstop(h);
-            mode = U_FROM_Z;
-            t_z = t_new;
-            // ---- D^T alpha, D^T u and the dual residual norms ---------------------------------------
-            h = P->tstart(MVTV_K_GATHER);
-            const int hb = P->tstart_b(MVTV_K_GATHER4B);
-            np = L.grid;
-            if (P->e3d)
-                HIP_TRY(launch_gather3d(P->g, P->order, U_FROM_Z, P->stream, P->edges, t_z, P->ga, gnew, gprev, c_prev,
-                                        P->partials, &np, nullptr, P->g4));
-            else
-                HIP_TRY(launch_gather(P->g, P->order, U_FROM_Z, L, P->edges, t_z, P->ga, gnew, gprev, c_prev, P->partials));
-            P->tstop(h);
-            P->tstop_b(hb);
-            h = P->tstart(MVTV_K_REDUCE);
-            HIP_TRY(launch_finalize(P->stream, P->partials, np, GR_N, 0, 0, P->red + ER_N, P->st));
-            P->tstop(h);
-        }
-        HIP_TRY(hipMemcpyAsync(P->host_red, P->red, (ER_N + GR_N) * sizeof(double), hipMemcpyDeviceToHost, P->stream));
-        HIP_TRY(hipStreamSynchronize(P->stream));   // timing events are harvested after the loop
-        const double* R = P->host_red;
-        const double r_norm = std::sqrt(R[ER_R2]);
-        it += 1;
-        counter += 1;
-        double c_next = 1.0, rho_next = rho;
-        if (variant == MVTV_VARIANT_RCPP) {
-            // :117-125
-            dual_norm = std::fabs(rho) * std::sqrt(R[ER_N + GR_S2B]);
-            primal_norm = r_norm;
-            eps_dual = tol * (std::sqrt(N) + std::sqrt(R[ER_N + GR_GU2]));
-            eps_primal = tol * (std::sqrt(E) + std::max(std::sqrt(R[ER_D2]), std::sqrt(R[ER_A2])));
-            const double tau = 2.0;
-            if (primal_norm > 10 * dual_norm) {
-                rho_next = tau * rho;
-                c_next = 1.0 / tau;
-            } else if (dual_norm > 10 * primal_norm) {
-                rho_next = 1.0 / tau * rho;
-                c_next = tau;
-            }
-            S.s_norm = dual_norm;
-            S.eps_pri = eps_primal;
-            S.eps_dual = eps_dual;
-        } else if (variant == MVTV_VARIANT_CPP) {
-            // :118-126 — s uses the new alpha and the old u; rho is an int
-            const double s_norm = std::fabs(rho) * std::sqrt(R[ER_N + GR_S2A]);
-            dtheta = R[ER_DTH];
-            S.s_norm = s_norm;
-            if (o.fixed_iters <= 0 && counter > max_counter) {
-                status = MVTV_MAXITER;
-                fail(status, "Failed to converge!");
-                rho_next = rho;
-            } else {
-                if (r_norm > 20 * s_norm) {
-                    rho_next = 20 * rho;
-                    c_next = 0.05;
-                } else if (s_norm > 20 * r_norm) {
-                    rho_next = 0.1 * rho;
-                    c_next = 10.0;
-                }
-                rho_next = double(int(rho_next));
-            }
-        } else {
-            dtheta = R[ER_DTH];
-        }
-        S.r_norm = r_norm;
-        S.dtheta_max = dtheta;
-        std::swap(gprev, gnew);
-        c_prev = c_next;
-        rho = rho_next;
-        if (variant == MVTV_VARIANT_RCPP) sigma = rho;   // spcrosses = crossO + rho crossD (:126)
-        if (status == MVTV_MAXITER) break;
-        if (variant == MVTV_VARIANT_RCPP && o.fixed_iters <= 0 && counter > max_counter) {
-            if (o.verbose) std::printf("ADMM reached max_counter at lambda = %g\n", lambda);
-            status = MVTV_MAXITER;
-            break;
-        }
-    }
-    P->harvest();   // the stream is idle here (last iteration synchronised)
-    twin_guard.armed = false;
-    if (twin) {
-        HIP_TRY(fill_twins(P->g, P->order, P->stream, P->edges));
-        HIP_TRY(hipStreamSynchronize(P->stream));
-    }
-    if (o.verbose) std::printf("Lambda= %g, Counter = %d\n", lambda, counter);
-    // keep the resident state consistent: g_uprev buffer is P->guprev
-    if (gprev != P->guprev) std::swap(P->guprev, P->gu);
-    P->edge_mode = mode;
-    P->t_z = t_z;
-    P->c_state = c_prev;
-    P->rho = rho;
-    S.iters = it;
-    S.theta_solver = spectral ? MVTV_SOLVER_SPECTRAL : (pcg_spec ? MVTV_SOLVER_PCG_SPECTRAL : MVTV_SOLVER_PCG);
-    S.rho = rho;
-    S.status = status;
-    S.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (stats) *stats = S;
-    return status;
 }
 
 mvtv_status mvtv_admm(mvtv_problem* P, const mvtv_admm_opts* opts, double lambda, double* theta_inout,

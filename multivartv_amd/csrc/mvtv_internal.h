@@ -159,7 +159,7 @@ struct PcgState {
     int32_t pad;
 };
 
-// Device-resident ADMM control (asynchronous loop, mvtv_capi.cpp): the scalars the kernels of one
+// Device-resident ADMM control (asynchronous loop, mvtv_admm.cpp): the scalars the kernels of one
 // iteration consume, written by k_admm_control at the end of each iteration. Every kernel of the
 // loop returns at once when `done` is set, so the host can enqueue iterations ahead of the decision.
 struct AdmmCtl {
@@ -257,7 +257,7 @@ hipError_t launch_finalize(hipStream_t s, const double* partials, int nparts, in
                            PcgState* st, double rtol2 = 0.0, int maxit = 0, const AdmmCtl* ctl = nullptr,
                            AdmmCtl* ctl_step = nullptr, const double* step_red = nullptr);
 // end of an asynchronous ADMM iteration: red = [|r|^2, |D theta|^2, |alpha|^2, max dtheta, |g_u|^2,
-// |s_B|^2, |s_A|^2]; adapt_step, stopping test and the next iteration's scalars (mvtv_capi.cpp mirror)
+// |s_B|^2, |s_A|^2]; adapt_step, stopping test and the next iteration's scalars (mvtv_admm.cpp mirror)
 hipError_t launch_admm_control(hipStream_t s, AdmmCtl* ctl, const double* red);
 // fused 3-D Chronopoulos-Gear PCG (mvtv_cg3d.hip): mode 0 prologue, 1 first iteration, 2 iteration;
 // partials get 4 values per workgroup (gamma, delta, |r|^2, |b|^2), *nblocks_out workgroups

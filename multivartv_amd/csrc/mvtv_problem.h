@@ -1,9 +1,11 @@
 // mvtv_problem.h — the mvtv_problem handle and host helpers shared by the C-ABI translation units
-// (mvtv_capi.cpp: single-GPU ADMM, operators, setup; mvtv_slab.cpp: the slab-decomposed loop over RCCL).
+// (mvtv_capi.cpp: setup, theta-solves, operators, batch calls, instrumentation; mvtv_admm.cpp: the ADMM loop of one
+// GPU and the parts of an iteration it shares with the slab loop; mvtv_slab.cpp: the slab-decomposed loop over RCCL).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -92,10 +94,6 @@ struct mvtv_problem {
     bool f4d = false;             // fused 4-D edge update + gather pass A (k_admm4a; second edge buffer, g4)
     double* edges2 = nullptr;     // ping-pong partner of edges for the fused kernel
     bool zpicked = false;         // the z ping-pong pair was chosen by timed probes (pick_zpair)
-    double* edges3 = nullptr;     // third z buffer of the spectral loop (MVTV_EBUF3=1). On boxes where the fused
-                                  // launches alternate fast / slow, the slow ones are those writing into
-                                  // `edges` (measured 4.60 / 4.97 ms alternating -> 4.60 / 4.53 / 5.00);
-                                  // +7.5 GB at 512^3
     double* pcg_b = nullptr;      // right-hand side of the spectrally preconditioned PCG
     double* g4 = nullptr;         // 4 N-arrays: the two-pass 4-D gather's partial sums
     double wmean = 1.0;           // mean(W): the preconditioner's identity weight
@@ -111,13 +109,6 @@ struct mvtv_problem {
     AdmmCtl* ctl = nullptr;       // device control block of the asynchronous ADMM loop
     AdmmCtl* host_ctl = nullptr;  // pinned mirror
     int admm_hint = 0;            // ADMM iterations of the last converged run (enqueue-ahead depth)
-    // the asynchronous loop's two-iteration launch sequence captured as a HIP graph (mvtv_capi.cpp), valid while the
-    // buffers and flags it was captured with (graph_key) are unchanged
-    struct LoopGraph {
-        std::vector<const void*> key;
-        hipGraphExec_t exec = nullptr;   // nullptr: the capture failed, stream launches for this key
-    };
-    std::vector<LoopGraph> graphs;
 
     // batched small-mesh fits (mvtv_path_batch, mvtv_solve_batch)
     int batch_cos = 0;            // mvtv_problem_batch_cosine: 0 Jacobi-PCG for all, 1 exact cosine solve for W = I
@@ -210,5 +201,60 @@ struct mvtv_problem {
     }
 };
 
-// timed choice of the fused 3-D kernel's z ping-pong buffer pair, once per problem (mvtv_capi.cpp pick_zpair)
-mvtv_status zpair_pick(mvtv_problem* P, bool track_theta, bool twin);
+namespace mvtv {
+// ---- mvtv_capi.cpp: what the ADMM loop needs of the setup and the theta-solves
+double variant_tol(const mvtv_admm_opts& o);
+int variant_maxc(const mvtv_admm_opts& o);
+mvtv_status ensure_state(mvtv_problem* P);
+bool spectral_ok(const mvtv_problem* P);
+bool split_on(const mvtv_problem* P);
+mvtv_status spectral_solve(mvtv_problem* P, double sigma, const double* oty, const double* ga, double ca,
+                           const double* gb, double cb, double* x, const AdmmCtl* ctl = nullptr, double w0 = 1.0,
+                           const int32_t* skip = nullptr, bool fold = false);
+mvtv_status pcgs_solve(mvtv_problem* P, double sigma, const double* oty, const double* ga, double ca,
+                       const double* gb, double cb, double* x, double rtol, int maxit, int* iters, double* relres);
+mvtv_status pcg_solve(mvtv_problem* P, double sigma, const double* oty, const double* ga, double ca,
+                      const double* gb, double cb, double* x, double rtol, int maxit, int* iters, double* relres);
+
+// ---- mvtv_admm.cpp: the part of an ADMM iteration after the theta-solve, shared by the device-controlled loop, the
+// host-controlled loop and the slab loop. The edge work of one iteration:
+struct EdgePass {
+    int umode = U_FROM_Z;                        // how the edge buffer holds u on entry (U_EXPLICIT: a run's first pass)
+    const double* z_old = nullptr;               // z ping-pong; z_new == z_old where the layout updates in place
+    double* z_new = nullptr;
+    double* g_new = nullptr;                     // D^T u of this iteration, and the previous one's
+    const double* g_prev = nullptr;
+    const double* theta_old = nullptr;           // max|theta - theta_old| wanted (variants A, C), or null
+    const AdmmCtl* ctl = nullptr;                // the kernels take thresholds and scales from the control block, and skip
+                                                 // once it says done; then the by-value scalars keep these neutral values
+    double t_old = 0.0, c_old = 1.0, t_new = 0.0, c_prev = 1.0;
+    bool fold = false, twin = false;
+    bool timed_red = false;                      // the reductions are counted under MVTV_K_REDUCE
+    bool ctl_step = false;                       // the last reduction also runs the control step on P->ctl
+};
+// edge stage: the edge update (fused with the gather, or with its pass A, where the mesh allows) and its sums into
+// P->red; gather stage: what is left of D^T alpha and D^T u, and its sums into P->red + ER_N. Two calls, so that the
+// slab loop can move its z halo between them.
+mvtv_status edge_stage(mvtv_problem* P, const EdgePass& e);
+mvtv_status gather_stage(mvtv_problem* P, const EdgePass& e);
+
+// the device-controlled loops (one GPU's and the slab's): the control block at the start of a run, enqueued on P->stream
+mvtv_status admm_ctl_start(mvtv_problem* P, int variant, int fixed_iters, int max_counter, double tol, double lambda,
+                           double rho, double sigma, double c_prev, double t_z, double dtheta, double sqrtN,
+                           double sqrtE);
+// enqueue iterations ahead of the device's decisions and poll the control block (left in P->host_ctl) until it says
+// done or `limit` iterations are enqueued. First poll after fixed_iters, else the last converged run's count, else 16;
+// then every max(4, enq / 4). single: one iteration per poll. mark: the first timing entry of each iteration
+mvtv_status admm_enqueue_ahead(mvtv_problem* P, const std::function<mvtv_status(int)>& enqueue, int fixed_iters,
+                               int limit, bool single, std::vector<size_t>& mark);
+// after the last poll: timing entries of the iterations past the stop dropped and the rest harvested, the ping-pong
+// parities (D^T u; z with `pingpong`) put back so that P->guprev and P->edges hold the state, the resident scalars and
+// the stats the control block gives. The caller adds the solver, its PCG counts and the seconds
+mvtv_admm_stats admm_finish(mvtv_problem* P, const std::vector<size_t>& mark, int fixed_iters, bool fold, bool pingpong);
+
+// The fused kernels may skip the twin blocks (mvtv_internal.h twin_block) of a one-GPU problem; their edge words
+bool twin_ready(const mvtv_problem* P);
+double twin_edges(const mvtv_problem* P);
+// timed choice of the fused 3-D kernel's z ping-pong buffer pair, once per problem
+mvtv_status pick_zpair(mvtv_problem* P, bool track_theta, bool twin);
+}  // namespace mvtv

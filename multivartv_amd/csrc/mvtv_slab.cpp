@@ -876,7 +876,7 @@ mvtv_status slab_run(mvtv_problem* P, mvtv_comm* C, const mvtv_admm_opts* opts, 
     // every block of the halo)
     const bool twin = (fused || fused4) && twin_weights_equal(P->g, P->order) && !probe_env("MVTV_TWIN_OFF");
     if (P->timing && (fused || fused4)) P->twin_timed = twin;
-    // folded right-hand side (as mvtv_capi.cpp's loop): the fused kernel stores s = rho (D^T alpha + D^T u) and the
+    // folded right-hand side (as mvtv_admm.cpp's loop): the fused kernel stores s = rho (D^T alpha + D^T u) and the
     // next first pass reads oty + s (oty + (rho'/rho) s + rho' (c - 1) D^T u after a rho change)
     const uint32_t m0 = P->g.m[0];
     const bool fold_path = fused ? P->g.p == 3 : (P->g.p == 4 && P->e3d && P->g4 != nullptr && gather4_ok(P->g));
@@ -899,7 +899,7 @@ mvtv_status slab_run(mvtv_problem* P, mvtv_comm* C, const mvtv_admm_opts* opts, 
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess) ndev = 0;
     const bool shared_device = G > 1 && ndev > 0 && G > ndev;
-    if (fused && !P->zpicked && !shared_device) MVTV_TRY(zpair_pick(P, false, twin));
+    if (fused && !P->zpicked && !shared_device) MVTV_TRY(pick_zpair(P, false, twin));
     const size_t nodes = P->g.N, ebytes = size_t(P->g.nb) * nodes * sizeof(double);
 
     // ---- initial state: theta0 everywhere (ghosts included), u0 = 0, g_alpha = D^T D theta0 -----------
@@ -908,35 +908,20 @@ mvtv_status slab_run(mvtv_problem* P, mvtv_comm* C, const mvtv_admm_opts* opts, 
     if (pingpong) HIP_TRY(hipMemsetAsync(P->edges2, 0, ebytes, s));
     HIP_TRY(hipMemsetAsync(P->guprev, 0, nodes * sizeof(double), s));
     HIP_TRY(launch_apply_A(P->g, P->L(), 1.0, W_NONE, nullptr, P->theta, P->ga, nullptr, nullptr));
-    AdmmCtl& c = *P->host_ctl;
-    std::memset(&c, 0, sizeof(c));
-    c.variant = MVTV_VARIANT_RCPP;
-    c.fixed_iters = opts->fixed_iters > 0 ? opts->fixed_iters : 0;
-    c.max_counter = max_counter;
-    c.lambda = lambda;
-    c.tol = tol;
-    c.sqrtN = std::sqrt(double(P->g.N / P->g.m[p - 1]) * double(sg.mg));
-    {   // global edge count: sum over blocks of prod_j (m_j - [j in S']) with the global last extent
-        double E = 0.0;
-        for (int k = 0; k < P->g.nb; ++k) {
-            double len = 1.0;
-            for (int j = 0; j < p; ++j) {
-                const double mj = j == p - 1 ? double(sg.mg) : double(P->g.m[j]);
-                len *= mj - double((P->sprime[k] >> j) & 1);
-            }
-            E += len;
+    P->edge_mode = U_EXPLICIT;   // the resident state is this zeroed one until an iteration has run
+    P->t_z = 0.0;
+    double E = 0.0;   // global edge count: sum over blocks of prod_j (m_j - [j in S']) with the global last extent
+    for (int k = 0; k < P->g.nb; ++k) {
+        double len = 1.0;
+        for (int j = 0; j < p; ++j) {
+            const double mj = j == p - 1 ? double(sg.mg) : double(P->g.m[j]);
+            len *= mj - double((P->sprime[k] >> j) & 1);
         }
-        c.sqrtE = std::sqrt(E);
+        E += len;
     }
-    c.rho = rho0;
-    c.sigma = rho0;
-    c.c_prev = 1.0;
-    c.t_z = 0.0;
-    c.t_next = lambda / rho0;
-    c.counter = 1;
-    c.dual_norm = c.primal_norm = 1.0;
-    c.eps_dual = c.eps_pri = tol;
-    HIP_TRY(hipMemcpyAsync(P->ctl, &c, sizeof(AdmmCtl), hipMemcpyHostToDevice, s));
+    MVTV_TRY(admm_ctl_start(P, MVTV_VARIANT_RCPP, opts->fixed_iters, max_counter, tol, lambda, rho0, rho0, 1.0, 0.0, 0.0,
+                            std::sqrt(double(P->g.N / P->g.m[p - 1]) * double(sg.mg)), std::sqrt(E)));
+    const AdmmCtl& c = *P->host_ctl;   // as of the last poll; pcg_theta reads the iteration's rho and sigma from it
 
     // geometry of the owned planes (local passes) and of this rank's line chunk (the last dimension)
     Geom og = P->g;
@@ -1241,75 +1226,35 @@ mvtv_status slab_run(mvtv_problem* P, mvtv_comm* C, const mvtv_admm_opts* opts, 
             }
             if (!solo) HIP_TRY(hipStreamWaitEvent(s, ev[EV_THD], 0));
         }
-        // -- edge update + gather on the owned planes, partial sums into P->red
-        if (fused) {
-            if (zh_pending) HIP_TRY(hipStreamWaitEvent(s, ev[EV_ZH], 0));   // z_old's ghost plane is in place
-            int h = P->tstart(MVTV_K_ADMM_FUSED);
-            int npf = 0;
-            HIP_TRY(launch_admm3d(P->g, P->order, um, s, P->theta, zo, zn, 0.0, 1.0, 0.0, 1.0, nullptr, P->ga, gn, gp,
-                                  P->partials, &npf, P->ctl, fold, twin));
-            P->tstop(h);
-            HIP_TRY(launch_finalize(s, P->partials, npf, ER_N + GR_N, -(1 << ER_DTH), 0, P->red, P->st, 0.0, 0, P->ctl));
-        } else if (fused4) {
-            // z_new and pass A's sums of the owned planes in one pass; then the last owned plane of z_new to rank+1's
-            // lower ghost plane, pass A on this rank's ghost plane (pass B at the first owned plane needs its Gw), pass B
-            int h = P->tstart(MVTV_K_ADMM_FUSED4);
-            int npe = 0;
-            HIP_TRY(launch_admm4a(P->g, P->order, um, s, P->theta, zo, zn, 0.0, 1.0, 0.0, nullptr, P->g4, P->partials,
-                                  &npe, P->ctl, twin));
-            P->tstop(h);
-            HIP_TRY(launch_finalize(s, P->partials, npe, ER_N, 1, 0, P->red, P->st, 0.0, 0, P->ctl));
-            if (!solo && twin && rk < G - 1)
+        // -- edge update + gather on the owned planes, partial sums into P->red (mvtv_admm.cpp's two stages, the
+        //    thresholds and scales from the control block; the reductions are not timed)
+        if (zh_pending) HIP_TRY(hipStreamWaitEvent(s, ev[EV_ZH], 0));   // fused: z_old's ghost plane is in place
+        EdgePass e;
+        e.umode = um;
+        e.z_old = zo;
+        e.z_new = zn;
+        e.g_new = gn;
+        e.g_prev = gp;
+        e.ctl = P->ctl;
+        e.fold = fold;
+        e.twin = twin;
+        MVTV_TRY(edge_stage(P, e));
+        if (!fused && !solo) {
+            // D^T at the first owned plane reads the new z of plane zb-1: the last owned plane of z_new to rank+1's
+            // lower ghost plane. 4-D: with its twins filled first, and then pass A on this rank's ghost plane (pass B
+            // at the first owned plane needs its Gw)
+            if (fused4 && twin && rk < G - 1)
                 HIP_TRY(fill_twins(P->g, P->order, s, zn, uint32_t(last_owned), uint32_t(last_owned + pl)));
-            if (!solo) {
-                MVTV_TRY(handoff(ev[EV_EDGE], s, sc));
-                lane(1);
-                MVTV_TRY(C->begin());
-                if (rk < G - 1) MVTV_TRY(edge_plane_xfer(zn, last_owned / pl, rk + 1, true));
-                if (rk > 0) MVTV_TRY(edge_plane_xfer(zn, 0, rk - 1, false));
-                MVTV_TRY(C->end(sc));
-                MVTV_TRY(handoff(ev[EV_EDGED], sc, s));
-                if (rk > 0) HIP_TRY(launch_gather4a_ghost(P->g, P->order, s, zn, P->g4, P->ctl));
-            }
-            h = P->tstart(MVTV_K_GATHER4B);
-            int npg = 0;
-            HIP_TRY(launch_gather4b(P->g, U_FROM_Z, s, P->ga, gn, gp, 1.0, P->partials, &npg, P->ctl, P->g4, fold));
-            P->tstop(h);
-            HIP_TRY(launch_finalize(s, P->partials, npg, GR_N, 0, 0, P->red + ER_N, P->st, 0.0, 0, P->ctl));
-        } else {
-            int h = P->tstart(MVTV_K_EDGE_UPDATE);
-            int npe = P->grid;
-            if (P->e3d)
-                HIP_TRY(launch_edge3d(P->g, P->order, um, s, P->theta, P->edges, 0.0, 1.0, 0.0, nullptr, P->partials,
-                                      &npe, P->ctl));
-            else
-                HIP_TRY(launch_edge_update(P->g, P->order, um, P->L(), P->theta, P->edges, 0.0, 1.0, 0.0, nullptr,
-                                           P->partials, P->ctl));
-            P->tstop(h);
-            HIP_TRY(launch_finalize(s, P->partials, npe, ER_N, 1, 0, P->red, P->st, 0.0, 0, P->ctl));
-            // D^T at the first owned plane reads the new z of plane zb-1 (rank-1's last plane)
-            if (!solo) {
-                MVTV_TRY(handoff(ev[EV_EDGE], s, sc));
-                lane(1);
-                MVTV_TRY(C->begin());
-                if (rk < G - 1) MVTV_TRY(edge_plane_xfer(P->edges, last_owned / pl, rk + 1, true));
-                if (rk > 0) MVTV_TRY(edge_plane_xfer(P->edges, 0, rk - 1, false));
-                MVTV_TRY(C->end(sc));
-                MVTV_TRY(handoff(ev[EV_EDGED], sc, s));
-            }
-            h = P->tstart(MVTV_K_GATHER);
-            const int hb = P->tstart_b(MVTV_K_GATHER4B);
-            int npg = P->grid;
-            if (P->e3d)
-                HIP_TRY(launch_gather3d(P->g, P->order, U_FROM_Z, s, P->edges, 0.0, P->ga, gn, gp, 1.0, P->partials,
-                                        &npg, P->ctl, P->g4, fold));
-            else
-                HIP_TRY(launch_gather(P->g, P->order, U_FROM_Z, P->L(), P->edges, 0.0, P->ga, gn, gp, 1.0,
-                                      P->partials, P->ctl));
-            P->tstop(h);
-            P->tstop_b(hb);
-            HIP_TRY(launch_finalize(s, P->partials, npg, GR_N, 0, 0, P->red + ER_N, P->st, 0.0, 0, P->ctl));
+            MVTV_TRY(handoff(ev[EV_EDGE], s, sc));
+            lane(1);
+            MVTV_TRY(C->begin());
+            if (rk < G - 1) MVTV_TRY(edge_plane_xfer(zn, last_owned / pl, rk + 1, true));
+            if (rk > 0) MVTV_TRY(edge_plane_xfer(zn, 0, rk - 1, false));
+            MVTV_TRY(C->end(sc));
+            MVTV_TRY(handoff(ev[EV_EDGED], sc, s));
+            if (fused4 && rk > 0) HIP_TRY(launch_gather4a_ghost(P->g, P->order, s, zn, P->g4, P->ctl));
         }
+        MVTV_TRY(gather_stage(P, e));
         // -- global sums, then every rank's identical decision
         if (!solo) MVTV_TRY(crit_allreduce(P->red, ER_N + GR_N));
         HIP_TRY(launch_admm_control(s, P->ctl, P->red));
@@ -1337,56 +1282,24 @@ mvtv_status slab_run(mvtv_problem* P, mvtv_comm* C, const mvtv_admm_opts* opts, 
     // (W != I: one iteration per poll, the PCG needs the control block's sigma on the host)
     // (tolerance mode: the last converged run's count first, as the one-GPU loop, so a warm-started path enqueues
     // few iterations past its stop; every rank holds the same hint)
-    int target = wd ? 1 : (opts->fixed_iters > 0 ? opts->fixed_iters : (P->admm_hint > 0 ? P->admm_hint : 16));
-    int enq = 0;
     std::vector<size_t> mark;
-    for (;;) {
-        while (enq < target && enq < limit) {
-            mark.push_back(P->pending.size());
-            MVTV_TRY(enqueue(enq++));
-        }
-        HIP_TRY(hipMemcpyAsync(P->host_ctl, P->ctl, sizeof(AdmmCtl), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (c.done || enq >= limit) break;
-        target = wd ? enq + 1 : enq + std::max(4, enq / 4);
-    }
+    MVTV_TRY(admm_enqueue_ahead(P, enqueue, opts->fixed_iters, limit, wd, mark));
     if (!solo) HIP_TRY(hipStreamSynchronize(sc));   // the last z halo
-    const int it_done = c.it;
-    if (P->timing && it_done < int(mark.size()))
-        for (size_t e = mark[size_t(it_done)]; e < P->pending.size(); ++e) P->pending[e].kid = -1;
-    P->harvest();
-    if (P->timing && fold) P->fold_fix += c.nfix;
-    if (opts->fixed_iters <= 0 && c.status == 0) P->admm_hint = it_done + 1;
-    if (it_done & 1) {
-        std::swap(P->guprev, P->gu);
-        if (pingpong) std::swap(P->edges, P->edges2);
-    }
+    mvtv_admm_stats S = admm_finish(P, mark, opts->fixed_iters, fold, pingpong);
     if (twin) {
         HIP_TRY(fill_twins(P->g, P->order, s, P->edges));
         HIP_TRY(hipStreamSynchronize(s));
     }
     P->twin_ok = true;
-    P->edge_mode = it_done > 0 ? U_FROM_Z : U_EXPLICIT;
-    P->t_z = c.t_z;
-    P->c_state = c.c_prev;
-    P->rho = c.rho;
     P->have_state = true;
     P->u_default = false;
-    mvtv_admm_stats S{};
-    S.iters = it_done;
-    S.rho = c.rho;
-    S.r_norm = c.r_norm;
-    S.s_norm = c.s_norm;
-    S.eps_pri = c.eps_pri;
-    S.eps_dual = c.eps_dual;
     S.theta_solver = wd ? MVTV_SOLVER_PCG_SPECTRAL : MVTV_SOLVER_SPECTRAL;
     S.pcg_iters = pcg_total;
     S.pcg_iters_max = pcg_most;
     S.pcg_unconverged = pcg_unconv;
-    S.status = c.status ? MVTV_MAXITER : MVTV_OK;
     S.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (stats) *stats = S;
-    return S.status == MVTV_OK ? MVTV_OK : MVTV_MAXITER;
+    return mvtv_status(S.status);
 }
 }  // namespace
 

@@ -1,8 +1,8 @@
 """Textbook preconditioned conjugate gradients, the reference of the PCG tests (tests/test_gpu_parity.py,
 tests/test_gpu_pcg_scalars.py, tests/test_pcg_ref_host.py), and the two preconditioners the library's PCGs use.
 
-The library's three PCGs (the three-kernel one and the fused Chronopoulos-Gear k_cg3d of pcg_solve, mvtv_capi.cpp:262,
-and pcgs_solve with the cosine-transform preconditioner, mvtv_capi.cpp:702) are this method up to rounding, so their
+The library's three PCGs (the three-kernel one and the fused Chronopoulos-Gear k_cg3d of pcg_solve, and pcgs_solve
+with the cosine-transform preconditioner, both functions of mvtv_capi.cpp) are this method up to rounding, so their
 k-th iterate must equal x_k here to rounding. That is the one check that sees a wrong alpha or beta: x += alpha p and
 r -= alpha q stay consistent for any alpha, so a converged solve hides a lost partial sum."""
 import numpy as np
@@ -12,7 +12,7 @@ def pcg_iterates(A, Minv, b, x0, k, pq=None):
     """k iterations of PCG on A x = b from x0: ([x_1 .. x_k], [relres_1 .. relres_k]) with relres_i =
     sqrt(|r_i|^2 / |b|^2) of the recursive residual r_i = r_{i-1} - alpha q, the quantity k_finalize tests
     (mvtv_kernels.hip: bnorm2 = sum b^2 at :500 / :518, rnorm2 = sum r^2 at :514 / :535, done when rnorm2 <=
-    rtol^2 bnorm2 at :516 / :537; solve returns sqrt(rnorm2 / bnorm2), mvtv_capi.cpp:345 / :820).
+    rtol^2 bnorm2 at :516 / :537; pcg_solve and pcgs_solve of mvtv_capi.cpp return sqrt(rnorm2 / bnorm2) as relres).
 
     A and Minv are callables; the arithmetic runs in b's dtype (float64 or long double). ``pq(p, q)`` replaces the
     inner product p.q (tests/test_pcg_ref_host.py drops one workgroup's share with it)."""
@@ -56,8 +56,8 @@ def dtd_diagonal(m, blocks, dtype=np.float64):
 
 
 def dtd_diagonal_mean(m, blocks):
-    """mean over the mesh of diag(D^T D): sum_S cS[S] prod_{j in S} 2 (m_j - 1) / m_j (pcgs_solve's cmean,
-    mvtv_capi.cpp:709-716)."""
+    """mean over the mesh of diag(D^T D): sum_S cS[S] prod_{j in S} 2 (m_j - 1) / m_j (cmean in pcgs_solve,
+    mvtv_capi.cpp)."""
     acc = 0.0
     for blk in blocks:
         prod = blk.w * blk.w
@@ -68,9 +68,9 @@ def dtd_diagonal_mean(m, blocks):
 
 
 def spectral_preconditioner(m, blocks, W, sigma, solve, dtype=np.float64):
-    """M^-1 = S A0^-1 S of pcgs_solve (mvtv_capi.cpp:695-726): A0 = w0 I + sigma D^T D with w0 = mean(W) (:708),
+    """M^-1 = S A0^-1 S of pcgs_solve (mvtv_capi.cpp): A0 = w0 I + sigma D^T D with w0 = mean(W) (its w0),
     inverted exactly by ``solve(s, b)`` = (I + s D^T D)^-1 b as solve(sigma / w0, r) / w0; S = I while
-    std(W) < 0.1 dbar, dbar = w0 + sigma mean diag(D^T D) (:717-718), else S = diag(sqrt(dbar / d)) with d =
+    std(W) < 0.1 dbar, dbar = w0 + sigma mean diag(D^T D) (its dbar and scaled), else S = diag(sqrt(dbar / d)) with d =
     W + sigma diag(D^T D) (k_pcgs_sinv, mvtv_kernels.hip:668-674; applied to r before the solve and to z after it,
     k_pcgs_vec ops 0-2, :632-649). Returns (Minv, scaled)."""
     W = np.asarray(W, dtype=np.float64)

@@ -1,4 +1,4 @@
-"""pick_zpair (mvtv_capi.cpp): the placement-aware choice of the fused 3-D kernel's z buffer pair moves
+"""pick_zpair (mvtv_admm.cpp): the placement-aware choice of the fused 3-D kernel's z buffer pair moves
 the edge state between physical buffers and nothing else. A 256^3 problem (2^24 nodes, the smallest that
 takes the pick) runs 3 iterations, then 2 more resumed from the resident state, in fresh processes with
 the pick on, off and forced down its failure path; theta, rho and the residual norms must be identical

@@ -1,5 +1,5 @@
 # GPU box: A/B of environment switches on the 512^3 bench (same box, same binary, interleaved runs).
-# usage: AB_ENVS="MVTV_DCT_FASTDIV=1 MVTV_EBUF3=1" bash tools/gpu_ab_env.sh   (results under AB_OUT, default out/ab)
+# usage: AB_ENVS="MVTV_DCT_FASTDIV=1 MVTV_FOLD_OFF=1" bash tools/gpu_ab_env.sh   (results under AB_OUT, default out/ab)
 set -o pipefail
 R=$GRAFT_REPO_ROOT
 cd $R
