@@ -2964,13 +2964,17 @@ __global__ __launch_bounds__((NW * 64)) void k_blk_iface(const SpecArgs a, const
 // The planes of dim 2 split into C chunks [floor(m2 k / C), floor(m2 (k + 1) / C)) (k_trisr_iface's block rule);
 // workgroup b owns tile b % (m0 / 16) of chunk b / (m0 / 16). In place: a chunk reads and writes its own planes only,
 // plane i + 1 is read before it is written. The three launches are ordered by the stream alone.
-// r^(hi-i) by binary powering per step (the exponent is uniform over the workgroup): no division by r (r = 0 at
-// sigma = 0), and a factor that underflows belongs to a term below the result's rounding.
+// r^(hi-i) Bin by a two-level exponent (uniform over the workgroup): with hi - i = 8 a + b, b < 8, Bin's registers
+// hold Q = r^(8 a) Bin and a plane forms r^b Q with <= 2 squarings and <= 3 products; where a drops (b = 0 -> 7) Bin
+// is loaded again from lr into the same registers, issued at the end of the b = 0 step, and raised by (r^8)^a at
+// the start of the next (binary powering, once per 8 planes). No division by r (r = 0 at sigma = 0), and a factor
+// that underflows belongs to a term below the result's rounding. r^2, r^4 and r^8 are loop-invariant: their inputs
+// pass through an opaque copy so that they are recomputed, not kept in 48 more registers.
 // Registers: B, Fs, p (down) or r, F, Bin (up) and two planes' values, 16 doubles each; r (down) or scale / D (up) and
 // the twiddles sit in LDS beside the exchange buffer, so the loop holds no invariant loads the compiler could hoist
-// into registers (224 / 235 VGPRs, no scratch, 153 KB of LDS). One 512-thread workgroup per CU (L = 9). Barriers in
+// into registers (224 / 254 VGPRs, no scratch, 153 KB of LDS). One 512-thread workgroup per CU (L = 9). Barriers in
 // the plane loop order LDS only, so the next plane's loads, issued before this plane's stages, stay in flight. The
-// down sweep keeps p as a running product: powering it per plane as the up sweep must cost 577 against 449 us.
+// down sweep keeps p as a running product: powering it per plane cost 577 against 449 us.
 template <int L, bool UP>
 __global__ __launch_bounds__((spec8::Shape<L>::NT)) void k_sweep(const SpecArgs a, double* __restrict__ car,
                                                                   uint32_t m2, int C) {
@@ -3154,20 +3158,50 @@ __global__ __launch_bounds__((spec8::Shape<L>::NT)) void k_sweep(const SpecArgs 
         };
         issue(lo, cur, j0, tile * 16u + uint32_t(2 * c0));
         issue(lo + 1u, nxt, j0, tile * 16u + uint32_t(2 * c0));
+        // Bin's registers hold Q = r^(8 a) Bin while hi - i = 8 a + b, b < 8
+        auto requant = [&](uint32_t a8) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                double r8 = r[e];
+                asm volatile("" : "+v"(r8));   // r^8 is loop-invariant: recomputed here, not 16 more registers
+                r8 *= r8;
+                r8 *= r8;
+                r8 *= r8;
+                Bin[e] = rpow(r8, a8, Bin[e]);
+            }
+        };
+        requant((hi - lo) >> 3);
         for (uint32_t i = lo; i < hi; ++i) {
             MVTV_SWEEP_COORDS;
-            const uint32_t n = hi - i;
+            const uint32_t n = hi - i, b = n & 7u;
+            if (b == 7u && i > lo) requant(n >> 3);   // Bin reloaded at the end of the last step
             xbar<1>();   // the last stage of plane i - 1 has read its inputs
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 double xv[4];
 #pragma unroll
-                for (int e4 = 0; e4 < 4; ++e4) {
-                    const int e = 4 * s + e4;
-                    const double f = fma(-r[e], nxt[e], cur[e]);
-                    xv[e4] = s_lc[e * NT + t] * (cur[e] + rpow(r[e], n, Bin[e]) + r[e] * F[e]);
-                    F[e] = fma(r[e], F[e], f);
-                    cur[e] = nxt[e];
+                for (int h = 0; h < 2; ++h) {
+                    // r^b Q of the pair (k0, k0 + 1), b uniform: <= 2 squarings and <= 3 products each
+                    const int e0 = 4 * s + 2 * h;
+                    double rp[2] = {r[e0], r[e0 + 1]}, y[2] = {Bin[e0], Bin[e0 + 1]};
+                    asm volatile("" : "+v"(rp[0]), "+v"(rp[1]));   // r^2, r^4 are loop-invariant: not kept in registers
+                    if (b & 1u) y[0] *= rp[0], y[1] *= rp[1];
+                    if (b > 1u) {
+                        rp[0] *= rp[0], rp[1] *= rp[1];
+                        if (b & 2u) y[0] *= rp[0], y[1] *= rp[1];
+                        if (b > 3u) {
+                            rp[0] *= rp[0], rp[1] *= rp[1];
+                            y[0] *= rp[0], y[1] *= rp[1];
+                        }
+                    }
+#pragma unroll
+                    for (int e2 = 0; e2 < 2; ++e2) {
+                        const int e = e0 + e2;
+                        const double f = fma(-r[e], nxt[e], cur[e]);
+                        xv[2 * h + e2] = s_lc[e * NT + t] * (cur[e] + y[e2] + r[e] * F[e]);
+                        F[e] = fma(r[e], F[e], f);
+                        cur[e] = nxt[e];
+                    }
                 }
                 const int k = j + s * TPL;
                 const int ka = k, kb = k ? M - k : M / 2;
@@ -3185,6 +3219,18 @@ __global__ __launch_bounds__((spec8::Shape<L>::NT)) void k_sweep(const SpecArgs 
                     const double2 vb2 = cmul(q2, make_double2(Xmk.y, -Xk.y));
                     X[spec8::slot(ka, cx)] = make_double2(va1.x - vb1.y, va1.y + vb1.x);
                     X[spec8::slot(kb, cx)] = make_double2(va2.x - vb2.y, va2.y + vb2.x);
+                }
+            }
+            if (b == 0u) {   // the next 8 planes' Q starts from Bin again: into its own registers, a step ahead
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    const int k = j + s * TPL;
+                    const double* const p = car + (size_t(ck) * 2 + 1) * nl + k0;
+                    const double2 va = ldnt2(p + uint32_t(k) * m0), vb = ldnt2(p + uint32_t(k ? M - k : M / 2) * m0);
+                    Bin[4 * s] = va.x;
+                    Bin[4 * s + 1] = va.y;
+                    Bin[4 * s + 2] = vb.x;
+                    Bin[4 * s + 3] = vb.y;
                 }
             }
             issue(i + 2u, nxt, j, k0);   // in flight over the stages and the stores of plane i (plane i + 2: not written yet)
@@ -3604,8 +3650,10 @@ bool line_sweep_shape_ok(const Geom& g) {
 // Chunk count of the sweeps: the grid runs in rounds of the resident workgroups (occupancy x CUs), and a round lasts
 // as long as its longest chunk, plus the chunk's share of fixed work in plane steps: the line constants and the
 // pipeline's fill (~1) and the carries (8 words per line and chunk over the two sweeps and the interface, against the
-// 4 a plane step moves: 2). Ties take the fewer chunks. 0: no grid of >= one workgroup per CU with chunks of >= 8
-// planes (the auto gate). 512^3: 32 tiles x 8 chunks of 64 planes, one round of one workgroup a CU.
+// 4 a plane step moves: 2). The up sweep's reload of Bin, 1 word per line every 8 planes, grows with the planes and
+// not with the chunks (the chunk's first Q comes from the carry it loads anyway). Ties take the fewer chunks. 0: no
+// grid of >= one workgroup per CU with chunks of >= 8 planes (the auto gate). 512^3: 32 tiles x 8 chunks of 64 planes,
+// one round of one workgroup a CU.
 int line_sweep_chunks(const Geom& g, bool gate) {
     if (!line_sweep_shape_ok(g)) return 0;
     static thread_local int dev = -1, slots = 256, cus = 256;
