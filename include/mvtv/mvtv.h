@@ -48,10 +48,20 @@ typedef enum mvtv_variant {
     MVTV_VARIANT_PY = 2      /* C: code/solvers.py:53-76 (fixed rho = lambda, threshold 1) */
 } mvtv_variant;
 
-/* Row-block order of D. */
+/* Row-block order of D (low bit) and the rule that gives a block its difference set (bit 1).
+ * Orders 0 and 1 follow the reference: its mixedpartial differences along dim 0 first, so a mixed block whose
+ * set S misses dim 0 acts as S' = (S \ {min S}) + {0}, and a mesh with m_0 != m_{min S} is refused
+ * (MVTV_DIM_MISMATCH): every 3-D mesh with m_0 != m_1, every 4-D mesh unless m_0 = m_1 = m_2.
+ * Orders 2 and 3 keep the row order, the weights and the leading / dropped all-ones block of 0 and 1 and
+ * difference block b along exactly the dims whose bit is set in b (true mixed partials, D^T D =
+ * sum_S w_S^2 (x)_{j in S} L_j): any m_j >= 2 is accepted, no two blocks share a set, and E, the block
+ * lengths, mvtv_problem_block_info and the layout of u follow these sets. For p <= 2 both rules give the
+ * same D and orders 2, 3 compute bit for bit what 0, 1 compute. mvtv_problem_create_slab takes orders 0, 1 only. */
 typedef enum mvtv_block_order {
     MVTV_ORDER_CPP = 0,      /* C++ create_D: [all-ones, w=1] + b=1..2^p-2 (cpp-code/utils.cpp:245-269) */
-    MVTV_ORDER_PY = 1        /* Python create_D: b=1..2^p-1 unweighted, or b=1..2^p-2 weighted (code/utils.py:138-149) */
+    MVTV_ORDER_PY = 1,       /* Python create_D: b=1..2^p-1 unweighted, or b=1..2^p-2 weighted (code/utils.py:138-149) */
+    MVTV_ORDER_CPP_NOMINAL = 2, /* rows and weights of MVTV_ORDER_CPP, nominal difference sets */
+    MVTV_ORDER_PY_NOMINAL = 3   /* rows and weights of MVTV_ORDER_PY, nominal difference sets */
 } mvtv_block_order;
 
 /* Replaces the mbs_cache / mbs_one_inits bundles (rcpp…/solvers.hpp:30-50,
@@ -130,7 +140,8 @@ void mvtv_problem_destroy(mvtv_problem* prob);
 int64_t mvtv_problem_nodes(const mvtv_problem* prob);   /* N = ntheta (rcpp…/solvers.hpp:36) */
 int64_t mvtv_problem_edges(const mvtv_problem* prob);   /* E = rowsD (rcpp…/solvers.hpp:35) */
 int32_t mvtv_problem_blocks(const mvtv_problem* prob);
-/* block k's binary code, effective difference set S' (bit j = dim j) and weight */
+/* block k's binary code, difference set (bit j = dim j: S' under orders 0 and 1, the code's own dims under the
+ * nominal orders) and weight */
 mvtv_status mvtv_problem_block_info(const mvtv_problem* prob, int32_t k, int32_t* code, int32_t* sprime, double* weight);
 /* new O^T y and W for the same mesh (CV folds re-run create_cache_objects, rcpp…/solvers.cpp:347-348) */
 mvtv_status mvtv_problem_set_data(mvtv_problem* prob, const double* oty, const double* wdiag);

@@ -53,6 +53,10 @@ struct mbs_cache {
     // cpp-code/solvers.cpp:116). NaN: not set (B: rho_init, A: lambda). mbs_path (B) leaves the rho carried
     // INTO its last lambda here (:213), which mbs_fit_optimal's refit then solves with (:273, :47).
     double sp_sigma = std::numeric_limits<double>::quiet_NaN();
+    // set before create_cache_objects: the problem takes MVTV_ORDER_CPP_NOMINAL (true mixed partials, any mesh
+    // extents at p >= 3) instead of MVTV_ORDER_CPP; prob_order is the order `prob` was built with
+    bool nominal = false;
+    int prob_order = -1;
     mbs_cache() = default;
     mbs_cache(const mbs_cache&) = delete;
     mbs_cache& operator=(const mbs_cache&) = delete;
@@ -135,9 +139,12 @@ struct mbs_impl_result {
 // the device and mvtv_cv_batch returns none. Selection and the folds <= 1 refit (mbs_fit_optimal, on the matrix
 // crossO + rho crossD with the rho the final path carried into its last lambda) are unchanged; `verbose` prints
 // nothing for the batched paths.
+// nominal: every problem of the run (batched or not) is built with MVTV_ORDER_CPP_NOMINAL (mbs_cache::nominal), so a
+// 3-D or 4-D mesh of any extents is accepted; the default keeps the reference's rule and its MVTV_DIM_MISMATCH.
 struct mbs_impl_options {
     bool batched = false;
     int batch_cosine = 0;
+    bool nominal = false;
 };
 // mbs_impl (:305-376). mesh, ftrue, lambdas may be null (R's NULL). seed: kfoldinds. options: may be null (defaults).
 mbs_impl_result mbs_impl(const mat& data, const vec& y, const vec& m, const mat* mesh, int n_lambda,

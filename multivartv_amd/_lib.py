@@ -21,6 +21,9 @@ MVTV_OK, MVTV_MAXITER, MVTV_BAD_ARG, MVTV_DIM_MISMATCH = 0, 1, 2, 3
 MVTV_HIP_ERROR, MVTV_NO_DEVICE, MVTV_OUT_OF_MEMORY, MVTV_PCG_NOT_CONVERGED = 4, 5, 6, 7
 VARIANT_RCPP, VARIANT_CPP, VARIANT_PY = 0, 1, 2
 ORDER_CPP, ORDER_PY = 0, 1
+# the same row orders and weights with nominal difference sets (block b differences along the dims of its code):
+# any mesh extents at p >= 3, the same D as 0 / 1 for p <= 2
+ORDER_CPP_NOMINAL, ORDER_PY_NOMINAL = 2, 3
 KERNELS = ["edge_update", "gather_Dt", "pcg_init", "pcg_apply_A", "pcg_update", "pcg_direction", "reduce", "other",
            "pcg_fused3d", "dct_first", "dct", "admm_fused", "gather4_b", "dct_first_fold",
            "admm_fused4"]
@@ -175,7 +178,11 @@ def default_opts(variant=VARIANT_RCPP, **kw) -> AdmmOpts:
 
 
 class Problem:
-    """A mesh-TV problem resident on one GPU (wraps mvtv_problem)."""
+    """A mesh-TV problem resident on one GPU (wraps mvtv_problem).
+
+    ``order``: ORDER_CPP / ORDER_PY follow the reference's D, which refuses a 3-D mesh with m_0 != m_1 and a 4-D one
+    unless m_0 = m_1 = m_2 (DimMismatchError); ORDER_CPP_NOMINAL / ORDER_PY_NOMINAL keep their rows and weights and
+    take true mixed partials, on any mesh extents."""
 
     def __init__(self, m, oty, wdiag=None, deltas=None, order=ORDER_CPP, weighted=None, device=0):
         m = [int(v) for v in m]

@@ -26,6 +26,21 @@ namespace e3d {
 constexpr int TX = 64;
 }
 
+// f(ORD, NB) as integral constants for a problem's order and block count: the C++ row orders carry every block,
+// Python's weighted create_D drops the all-ones one
+template <int P, class F>
+static hipError_t dispatch_order_nb(const Geom& g, int order, F&& f) {
+    constexpr int FULL = (1 << P) - 1;
+    return dispatch_order<P>(order, [&](auto oc) {
+        if constexpr ((decltype(oc)::value & 1) == 0) {
+            return f(oc, std::integral_constant<int, FULL>{});
+        } else {
+            return g.nb == FULL - 1 ? f(oc, std::integral_constant<int, FULL - 1>{})
+                                    : f(oc, std::integral_constant<int, FULL>{});
+        }
+    });
+}
+
 struct Edge3dArgs {
     Geom g;
     const double* theta;
@@ -110,7 +125,7 @@ __global__ __launch_bounds__(NT) void k_edge3d(const Edge3dArgs a) {
                     if (!((q >> j) & 1)) v[q | (1 << j)] = v[q] - v[q | (1 << j)];
             static_for<0, NB>([&](auto kc) {
                 constexpr int k = decltype(kc)::value;
-                constexpr int S = sprime_mask(block_code(k, P, ORD), P);
+                constexpr int S = diff_mask(k, P, ORD);
                 {
                     const double d = g.w[k] * v[S];
                     double* ep = a.edges + eix(g, k, i);
@@ -163,7 +178,7 @@ __global__ __launch_bounds__(NT) void k_gather3d(const Edge3dArgs a) {
         // in-plane sums Q_k(e) for alpha and u of block k at plane e
         auto plane_q = [&](auto kc, int e, double& qa, double& qu) {
             constexpr int k = decltype(kc)::value;
-            constexpr int S = sprime_mask(block_code(k, P, ORD), P);
+            constexpr int S = diff_mask(k, P, ORD);
             constexpr int SI = S & 3;   // in-plane part of the difference set
             const uint32_t ic = uint32_t(e) * pl + base_xy;
             qa = 0.0;
@@ -187,7 +202,7 @@ __global__ __launch_bounds__(NT) void k_gather3d(const Edge3dArgs a) {
         if (T.z0 > 0) {   // carried sums of plane z0 - 1
             static_for<0, NB>([&](auto kc) {
                 constexpr int k = decltype(kc)::value;
-                constexpr int S = sprime_mask(block_code(k, P, ORD), P);
+                constexpr int S = diff_mask(k, P, ORD);
                 if constexpr ((S & 4) != 0) plane_q(kc, T.z0 - 1, qa_prev[k], qu_prev[k]);
             });
         }
@@ -195,7 +210,7 @@ __global__ __launch_bounds__(NT) void k_gather3d(const Edge3dArgs a) {
             double ga = 0.0, gu = 0.0;
             static_for<0, NB>([&](auto kc) {
                 constexpr int k = decltype(kc)::value;
-                constexpr int S = sprime_mask(block_code(k, P, ORD), P);
+                constexpr int S = diff_mask(k, P, ORD);
                 {
                     double qa, qu;
                     plane_q(kc, e, qa, qu);
@@ -301,19 +316,12 @@ hipError_t launch_edge3d(const Geom& g, int order, int umode, hipStream_t s, con
             klaunch(kern, dim3(grid), dim3(NT), 0, s, a);
             return hipGetLastError();
         };
-        if (order == 0) {
+        return dispatch_order_nb<3>(g, order, [&](auto oc, auto nbc) {
+            constexpr int O = decltype(oc)::value, NB = decltype(nbc)::value;
             if (umode == U_EXPLICIT)
-                return dth ? go(k_edge3d<0, U_EXPLICIT, true, NT, 7>) : go(k_edge3d<0, U_EXPLICIT, false, NT, 7>);
-            return dth ? go(k_edge3d<0, U_FROM_Z, true, NT, 7>) : go(k_edge3d<0, U_FROM_Z, false, NT, 7>);
-        }
-        if (g.nb == 6) {
-            if (umode == U_EXPLICIT)
-                return dth ? go(k_edge3d<1, U_EXPLICIT, true, NT, 6>) : go(k_edge3d<1, U_EXPLICIT, false, NT, 6>);
-            return dth ? go(k_edge3d<1, U_FROM_Z, true, NT, 6>) : go(k_edge3d<1, U_FROM_Z, false, NT, 6>);
-        }
-        if (umode == U_EXPLICIT)
-            return dth ? go(k_edge3d<1, U_EXPLICIT, true, NT, 7>) : go(k_edge3d<1, U_EXPLICIT, false, NT, 7>);
-        return dth ? go(k_edge3d<1, U_FROM_Z, true, NT, 7>) : go(k_edge3d<1, U_FROM_Z, false, NT, 7>);
+                return dth ? go(k_edge3d<O, U_EXPLICIT, true, NT, NB>) : go(k_edge3d<O, U_EXPLICIT, false, NT, NB>);
+            return dth ? go(k_edge3d<O, U_FROM_Z, true, NT, NB>) : go(k_edge3d<O, U_FROM_Z, false, NT, NB>);
+        });
     };
     if (a.ty == 8) return pick(std::integral_constant<int, 512>{});
     return pick(std::integral_constant<int, 256>{});
@@ -352,19 +360,12 @@ hipError_t launch_gather3d(const Geom& g, int order, int umode, hipStream_t s, c
             klaunch(kern, dim3(grid), dim3(NT), 0, s, a);
             return hipGetLastError();
         };
-        if (order == 0) {
+        return dispatch_order_nb<3>(g, order, [&](auto oc, auto nbc) {
+            constexpr int O = decltype(oc)::value, NB = decltype(nbc)::value;
             if (umode == U_EXPLICIT)
-                return prev ? go(k_gather3d<0, U_EXPLICIT, true, NT, 7>) : go(k_gather3d<0, U_EXPLICIT, false, NT, 7>);
-            return prev ? go(k_gather3d<0, U_FROM_Z, true, NT, 7>) : go(k_gather3d<0, U_FROM_Z, false, NT, 7>);
-        }
-        if (g.nb == 6) {
-            if (umode == U_EXPLICIT)
-                return prev ? go(k_gather3d<1, U_EXPLICIT, true, NT, 6>) : go(k_gather3d<1, U_EXPLICIT, false, NT, 6>);
-            return prev ? go(k_gather3d<1, U_FROM_Z, true, NT, 6>) : go(k_gather3d<1, U_FROM_Z, false, NT, 6>);
-        }
-        if (umode == U_EXPLICIT)
-            return prev ? go(k_gather3d<1, U_EXPLICIT, true, NT, 7>) : go(k_gather3d<1, U_EXPLICIT, false, NT, 7>);
-        return prev ? go(k_gather3d<1, U_FROM_Z, true, NT, 7>) : go(k_gather3d<1, U_FROM_Z, false, NT, 7>);
+                return prev ? go(k_gather3d<O, U_EXPLICIT, true, NT, NB>) : go(k_gather3d<O, U_EXPLICIT, false, NT, NB>);
+            return prev ? go(k_gather3d<O, U_FROM_Z, true, NT, NB>) : go(k_gather3d<O, U_FROM_Z, false, NT, NB>);
+        });
     };
     if (a.ty == 8) return pick(std::integral_constant<int, 512>{});
     return pick(std::integral_constant<int, 256>{});
@@ -414,15 +415,15 @@ template <int NB, int ORD>
 __host__ __device__ constexpr int f3a_nimg() {
     int n = 0;
     for (int k = 0; k < NB; ++k)
-        if ((sprime_mask(block_code(k, 3, ORD), 3) & 3) != 0) ++n;
+        if ((diff_mask(k, 3, ORD) & 3) != 0) ++n;
     return n;
 }
 template <int NB, int ORD>
 __host__ __device__ constexpr int f3a_slot(int k) {   // image slot of block k (-1: not in the image)
     int n = 0;
     for (int j = 0; j < k; ++j)
-        if ((sprime_mask(block_code(j, 3, ORD), 3) & 3) != 0) ++n;
-    return (sprime_mask(block_code(k, 3, ORD), 3) & 3) != 0 ? n : -1;
+        if ((diff_mask(j, 3, ORD) & 3) != 0) ++n;
+    return (diff_mask(k, 3, ORD) & 3) != 0 ? n : -1;
 }
 
 // TW (twin blocks, mvtv_internal.h twin_block): block KD carries the same numbers as block KC (same S', equal weight,
@@ -464,7 +465,7 @@ __device__ __forceinline__ void admm3a_tile(const Fused3dArgs& a, double* __rest
         const uint32_t i = uint32_t(e) * pl + ixy;
         static_for<0, NB>([&](auto kc) {
             constexpr int k = decltype(kc)::value;
-            constexpr int S = sprime_mask(block_code(k, P, ORD), P);
+            constexpr int S = diff_mask(k, P, ORD);
             const bool need = cell && (!hrow || (S & 2)) && (!hcol || (S & 1));
             if constexpr (TW && twin_of(k, P, ORD) != k) zo[k] = 0.0;
             else zo[k] = need ? a.z_old[eix(g, k, i)] : 0.0;
@@ -488,7 +489,7 @@ __device__ __forceinline__ void admm3a_tile(const Fused3dArgs& a, double* __rest
                 if (!((q >> j) & 1)) v[q | (1 << j)] = v[q] - v[q | (1 << j)];
         static_for<0, NB>([&](auto kc) {
             constexpr int k = decltype(kc)::value;
-            constexpr int S = sprime_mask(block_code(k, P, ORD), P);
+            constexpr int S = diff_mask(k, P, ORD);
             if constexpr (TW && twin_of(k, P, ORD) != k) {
                 zn[k] = 0.0;
             } else {
@@ -520,7 +521,7 @@ __device__ __forceinline__ void admm3a_tile(const Fused3dArgs& a, double* __rest
     // (x-1, y), (x, y-1), (x-1, y-1) from the image
     auto plane_q = [&](auto kc, int buf, double own_z, double& qa, double& qu) {
         constexpr int k = decltype(kc)::value;
-        constexpr int S = sprime_mask(block_code(k, P, ORD), P);
+        constexpr int S = diff_mask(k, P, ORD);
         constexpr int SI = S & 3;
         constexpr int sl = f3a_slot<NB, ORD>(k);
         qa = 0.0;
@@ -555,7 +556,7 @@ __device__ __forceinline__ void admm3a_tile(const Fused3dArgs& a, double* __rest
         if (inner) {
             static_for<0, NB>([&](auto kc) {
                 constexpr int k = decltype(kc)::value;
-                constexpr int S = sprime_mask(block_code(k, P, ORD), P);
+                constexpr int S = diff_mask(k, P, ORD);
                 if constexpr ((S & 4) != 0 && !(TW && twin_of(k, P, ORD) != k)) {
                     constexpr double mk = TW ? double(twin_count(k, NB, P, ORD)) : 1.0;   // exact for 2
                     double qa, qu;
@@ -591,7 +592,7 @@ __device__ __forceinline__ void admm3a_tile(const Fused3dArgs& a, double* __rest
             double ga = 0.0, gu = 0.0, na = 0.0, nu = 0.0;
             static_for<0, NB>([&](auto kc) {
                 constexpr int k = decltype(kc)::value;
-                constexpr int S = sprime_mask(block_code(k, P, ORD), P);
+                constexpr int S = diff_mask(k, P, ORD);
                 if constexpr (!(TW && twin_of(k, P, ORD) != k)) {
                     constexpr double mk = TW ? double(twin_count(k, NB, P, ORD)) : 1.0;
                     const double wk = mk * g.w[k];
@@ -791,17 +792,14 @@ hipError_t launch_admm3d(const Geom& g, int order, int umode, hipStream_t s, con
             return dth ? go(k_admm3a<O, U_EXPLICIT, true, NB, T>) : go(k_admm3a<O, U_EXPLICIT, false, NB, T>);
         return dth ? go(k_admm3a<O, U_FROM_Z, true, NB, T>) : go(k_admm3a<O, U_FROM_Z, false, NB, T>);
     };
-    using std::integral_constant;
-    using T1 = integral_constant<bool, true>;
-    using T0 = integral_constant<bool, false>;
-    if (order == 0)
-        return twin ? pick(integral_constant<int, 0>{}, integral_constant<int, 7>{}, T1{})
-                    : pick(integral_constant<int, 0>{}, integral_constant<int, 7>{}, T0{});
-    if (g.nb == 6)
-        return twin ? pick(integral_constant<int, 1>{}, integral_constant<int, 6>{}, T1{})
-                    : pick(integral_constant<int, 1>{}, integral_constant<int, 6>{}, T0{});
-    return twin ? pick(integral_constant<int, 1>{}, integral_constant<int, 7>{}, T1{})
-                : pick(integral_constant<int, 1>{}, integral_constant<int, 7>{}, T0{});
+    using T1 = std::integral_constant<bool, true>;
+    using T0 = std::integral_constant<bool, false>;
+    return dispatch_order_nb<3>(g, order, [&](auto oc, auto nbc) {
+        // no two blocks of a nominal order share a set: no TW form (twin is false there, twin_weights_equal)
+        if constexpr (twin_block(decltype(nbc)::value, 3, decltype(oc)::value) >= 0)
+            if (twin) return pick(oc, nbc, T1{});
+        return pick(oc, nbc, T0{});
+    });
 }
 
 // Fill block kdst of an edge state from block ksrc at nodes [i0, i1) (the twin block after a run that skipped it)
@@ -920,7 +918,7 @@ __global__ __launch_bounds__(e4d::NT) void k_edge4d(const Edge4dArgs a) {
                     if (!((q >> j) & 1)) v[q | (1 << j)] = v[q] - v[q | (1 << j)];
             static_for<0, NB>([&](auto kc) {
                 constexpr int k = decltype(kc)::value;
-                constexpr int S = sprime_mask(block_code(k, P, ORD), P);
+                constexpr int S = diff_mask(k, P, ORD);
                 const double d = g.w[k] * v[S];
                 double* ep = a.edges + eix(g, k, i);
                 const double stored = __builtin_nontemporal_load(ep);
@@ -988,16 +986,11 @@ hipError_t launch_edge4d(const Geom& g, int order, int umode, hipStream_t s, con
         klaunch(kern, dim3(grid), dim3(e4d::NT), 0, s, a);
         return hipGetLastError();
     };
-    if (order == 0) {
-        if (umode == U_EXPLICIT) return dth ? go(k_edge4d<0, U_EXPLICIT, true, 15>) : go(k_edge4d<0, U_EXPLICIT, false, 15>);
-        return dth ? go(k_edge4d<0, U_FROM_Z, true, 15>) : go(k_edge4d<0, U_FROM_Z, false, 15>);
-    }
-    if (g.nb == 14) {
-        if (umode == U_EXPLICIT) return dth ? go(k_edge4d<1, U_EXPLICIT, true, 14>) : go(k_edge4d<1, U_EXPLICIT, false, 14>);
-        return dth ? go(k_edge4d<1, U_FROM_Z, true, 14>) : go(k_edge4d<1, U_FROM_Z, false, 14>);
-    }
-    if (umode == U_EXPLICIT) return dth ? go(k_edge4d<1, U_EXPLICIT, true, 15>) : go(k_edge4d<1, U_EXPLICIT, false, 15>);
-    return dth ? go(k_edge4d<1, U_FROM_Z, true, 15>) : go(k_edge4d<1, U_FROM_Z, false, 15>);
+    return dispatch_order_nb<4>(g, order, [&](auto oc, auto nbc) {
+        constexpr int O = decltype(oc)::value, NB = decltype(nbc)::value;
+        if (umode == U_EXPLICIT) return dth ? go(k_edge4d<O, U_EXPLICIT, true, NB>) : go(k_edge4d<O, U_EXPLICIT, false, NB>);
+        return dth ? go(k_edge4d<O, U_FROM_Z, true, NB>) : go(k_edge4d<O, U_FROM_Z, false, NB>);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1059,7 +1052,7 @@ __global__ __launch_bounds__(64 * TYV) void k_gather4a(const Gather4Args a) {
     double ca0 = 0.0, cu0 = 0.0, caw = 0.0, cuw = 0.0;
     auto plane_q = [&](auto kc, int e, double& qa, double& qu) {
         constexpr int k = decltype(kc)::value;
-        constexpr int S = sprime_mask(block_code(k, P, ORD), P);
+        constexpr int S = diff_mask(k, P, ORD);
         constexpr int SI = S & 3;
         const uint32_t ib = uint32_t(e) * m01 + base;
         qa = 0.0;
@@ -1083,7 +1076,7 @@ __global__ __launch_bounds__(64 * TYV) void k_gather4a(const Gather4Args a) {
     if (z0 > 0) {
         static_for<0, NB>([&](auto kc) {
             constexpr int k = decltype(kc)::value;
-            constexpr int S = sprime_mask(block_code(k, P, ORD), P);
+            constexpr int S = diff_mask(k, P, ORD);
             if constexpr ((S & 4) != 0) {
                 double qa, qu;
                 plane_q(kc, z0 - 1, qa, qu);
@@ -1102,7 +1095,7 @@ __global__ __launch_bounds__(64 * TYV) void k_gather4a(const Gather4Args a) {
         double sa0 = 0.0, su0 = 0.0, saw = 0.0, suw = 0.0, na0 = 0.0, nu0 = 0.0, naw = 0.0, nuw = 0.0;
         static_for<0, NB>([&](auto kc) {
             constexpr int k = decltype(kc)::value;
-            constexpr int S = sprime_mask(block_code(k, P, ORD), P);
+            constexpr int S = diff_mask(k, P, ORD);
             double qa, qu;
             plane_q(kc, e, qa, qu);
             if constexpr ((S & 8) != 0) {
@@ -1251,9 +1244,10 @@ hipError_t launch_gather4(const Geom& g, int order, int umode, hipStream_t s, co
     };
     auto pick = [&](auto tc) {
         constexpr int T = decltype(tc)::value;
-        if (order == 0) return expl ? goa(k_gather4a<0, U_EXPLICIT, 15, T>) : goa(k_gather4a<0, U_FROM_Z, 15, T>);
-        if (g.nb == 14) return expl ? goa(k_gather4a<1, U_EXPLICIT, 14, T>) : goa(k_gather4a<1, U_FROM_Z, 14, T>);
-        return expl ? goa(k_gather4a<1, U_EXPLICIT, 15, T>) : goa(k_gather4a<1, U_FROM_Z, 15, T>);
+        return dispatch_order_nb<4>(g, order, [&](auto oc, auto nbc) {
+            constexpr int O = decltype(oc)::value, NB = decltype(nbc)::value;
+            return expl ? goa(k_gather4a<O, U_EXPLICIT, NB, T>) : goa(k_gather4a<O, U_FROM_Z, NB, T>);
+        });
     };
     const int ty = g4_ty();
     const hipError_t e = !(passes & 5) ? hipSuccess
@@ -1304,7 +1298,7 @@ constexpr int nt(bool tw) { return (ih(tw) + 1) * 64; }
 // image slots: the blocks whose S' has dim 0 or 1, minus the twins when they are skipped
 template <int NB, int ORD, bool TW = false>
 __host__ __device__ constexpr bool f4a_in_image(int k) {
-    return (sprime_mask(block_code(k, 4, ORD), 4) & 3) != 0 && !(TW && twin_of(k, 4, ORD) != k);
+    return (diff_mask(k, 4, ORD) & 3) != 0 && !(TW && twin_of(k, 4, ORD) != k);
 }
 template <int NB, int ORD, bool TW = false>
 __host__ __device__ constexpr int f4a_nimg() {
@@ -1392,7 +1386,7 @@ __global__ __launch_bounds__(f4a::nt(TW)) void k_admm4a(const Fused4Args a) {
             const uint32_t i = wo[0] + uint32_t(e) * pl + ixy;
             static_for<0, NB>([&](auto kc) {
                 constexpr int k = decltype(kc)::value;
-                constexpr int S = sprime_mask(block_code(k, P, ORD), P);
+                constexpr int S = diff_mask(k, P, ORD);
                 const bool need = cell && (!hrow || (S & 2)) && (!hcol || (S & 1));
                 if constexpr (TW && twin_of(k, P, ORD) != k) zo[k] = 0.0;
                 else zo[k] = need ? a.z_old[eix(g, k, i)] : 0.0;
@@ -1417,7 +1411,7 @@ __global__ __launch_bounds__(f4a::nt(TW)) void k_admm4a(const Fused4Args a) {
                     if (!((q >> j) & 1)) v[q | (1 << j)] = v[q] - v[q | (1 << j)];
             static_for<0, NB>([&](auto kc) {
                 constexpr int k = decltype(kc)::value;
-                constexpr int S = sprime_mask(block_code(k, P, ORD), P);
+                constexpr int S = diff_mask(k, P, ORD);
                 if constexpr (TW && twin_of(k, P, ORD) != k) {
                     zn[k] = 0.0;
                 } else {
@@ -1447,7 +1441,7 @@ __global__ __launch_bounds__(f4a::nt(TW)) void k_admm4a(const Fused4Args a) {
         };
         auto plane_q = [&](auto kc, int buf, double own_z, double& qa, double& qu) {
             constexpr int k = decltype(kc)::value;
-            constexpr int S = sprime_mask(block_code(k, P, ORD), P);
+            constexpr int S = diff_mask(k, P, ORD);
             constexpr int SI = S & 3;
             constexpr int sl = f4a_slot<NB, ORD, TW>(k);
             qa = 0.0;
@@ -1475,7 +1469,7 @@ __global__ __launch_bounds__(f4a::nt(TW)) void k_admm4a(const Fused4Args a) {
         auto carry = [&](int buf, const double (&zn)[NB], double& na0, double& nu0, double& naw, double& nuw) {
             static_for<0, NB>([&](auto kc) {
                 constexpr int k = decltype(kc)::value;
-                constexpr int S = sprime_mask(block_code(k, P, ORD), P);
+                constexpr int S = diff_mask(k, P, ORD);
                 if constexpr ((S & 4) != 0 && !(TW && twin_of(k, P, ORD) != k)) {
                     constexpr double mk = TW ? double(twin_count(k, NB, P, ORD)) : 1.0;
                     const double wk = mk * g.w[k];
@@ -1524,7 +1518,7 @@ __global__ __launch_bounds__(f4a::nt(TW)) void k_admm4a(const Fused4Args a) {
                 double sa0 = 0.0, su0 = 0.0, saw = 0.0, suw = 0.0, na0 = 0.0, nu0 = 0.0, naw = 0.0, nuw = 0.0;
                 static_for<0, NB>([&](auto kc) {
                     constexpr int k = decltype(kc)::value;
-                    constexpr int S = sprime_mask(block_code(k, P, ORD), P);
+                    constexpr int S = diff_mask(k, P, ORD);
                     if constexpr (!(TW && twin_of(k, P, ORD) != k)) {
                         constexpr double mk = TW ? double(twin_count(k, NB, P, ORD)) : 1.0;
                         const double wk = mk * g.w[k];
@@ -1629,7 +1623,7 @@ __global__ __launch_bounds__(f2d::NT) void k_admm2d(const Fused3dArgs a) {
                     if (!((q >> j) & 1)) v[q | (1 << j)] = v[q] - v[q | (1 << j)];
             static_for<0, NB>([&](auto kc) {
                 constexpr int k = decltype(kc)::value;
-                constexpr int S = sprime_mask(block_code(k, P, ORD), P);
+                constexpr int S = diff_mask(k, P, ORD);
                 const double d = g.w[k] * v[S];
                 const double uo = (UM == U_EXPLICIT) ? zo[k] : -c_old * clampd(zo[k], t_old);
                 const double z = cell ? d - uo : 0.0;
@@ -1647,7 +1641,7 @@ __global__ __launch_bounds__(f2d::NT) void k_admm2d(const Fused3dArgs a) {
         // in-row sums of block k at this cell: own z_new and (dim 0 in S') the lane below's
         auto row_q = [&](auto kc, const double (&zn)[NB], double& qa, double& qu) {
             constexpr int k = decltype(kc)::value;
-            constexpr int S = sprime_mask(block_code(k, P, ORD), P);
+            constexpr int S = diff_mask(k, P, ORD);
             const double v0 = zn[k];
             const double cl0 = clampd(v0, t_new);
             qa = v0 - cl0;
@@ -1669,7 +1663,7 @@ __global__ __launch_bounds__(f2d::NT) void k_admm2d(const Fused3dArgs a) {
             edge_cell(y0 - 1, r0, r1, zo, zn, false);
             static_for<0, NB>([&](auto kc) {
                 constexpr int k = decltype(kc)::value;
-                constexpr int S = sprime_mask(block_code(k, P, ORD), P);
+                constexpr int S = diff_mask(k, P, ORD);
                 double qa, qu;
                 row_q(kc, zn, qa, qu);
                 if constexpr ((S & 2) != 0) {
@@ -1697,7 +1691,7 @@ __global__ __launch_bounds__(f2d::NT) void k_admm2d(const Fused3dArgs a) {
             double ga = 0.0, gu = 0.0, na = 0.0, nu = 0.0;
             static_for<0, NB>([&](auto kc) {
                 constexpr int k = decltype(kc)::value;
-                constexpr int S = sprime_mask(block_code(k, P, ORD), P);
+                constexpr int S = diff_mask(k, P, ORD);
                 double qa, qu;
                 row_q(kc, zn, qa, qu);
                 ga = fma(g.w[k], qa, ga);
@@ -1806,16 +1800,11 @@ hipError_t launch_admm2d(const Geom& g, int order, int umode, hipStream_t s, con
         klaunch(kern, dim3(grid), dim3(f2d::NT), 0, s, a);
         return hipGetLastError();
     };
-    if (order == 0) {
-        if (umode == U_EXPLICIT) return dth ? go(k_admm2d<0, U_EXPLICIT, true, 3>) : go(k_admm2d<0, U_EXPLICIT, false, 3>);
-        return dth ? go(k_admm2d<0, U_FROM_Z, true, 3>) : go(k_admm2d<0, U_FROM_Z, false, 3>);
-    }
-    if (g.nb == 2) {
-        if (umode == U_EXPLICIT) return dth ? go(k_admm2d<1, U_EXPLICIT, true, 2>) : go(k_admm2d<1, U_EXPLICIT, false, 2>);
-        return dth ? go(k_admm2d<1, U_FROM_Z, true, 2>) : go(k_admm2d<1, U_FROM_Z, false, 2>);
-    }
-    if (umode == U_EXPLICIT) return dth ? go(k_admm2d<1, U_EXPLICIT, true, 3>) : go(k_admm2d<1, U_EXPLICIT, false, 3>);
-    return dth ? go(k_admm2d<1, U_FROM_Z, true, 3>) : go(k_admm2d<1, U_FROM_Z, false, 3>);
+    return dispatch_order_nb<2>(g, order, [&](auto oc, auto nbc) {   // the nominal orders: the kernels of 0 and 1
+        constexpr int O = decltype(oc)::value, NB = decltype(nbc)::value;
+        if (umode == U_EXPLICIT) return dth ? go(k_admm2d<O, U_EXPLICIT, true, NB>) : go(k_admm2d<O, U_EXPLICIT, false, NB>);
+        return dth ? go(k_admm2d<O, U_FROM_Z, true, NB>) : go(k_admm2d<O, U_FROM_Z, false, NB>);
+    });
 }
 
 
@@ -1881,17 +1870,13 @@ hipError_t launch_admm4a(const Geom& g, int order, int umode, hipStream_t s, con
             return dth ? go(k_admm4a<O, U_EXPLICIT, true, NB, T>) : go(k_admm4a<O, U_EXPLICIT, false, NB, T>);
         return dth ? go(k_admm4a<O, U_FROM_Z, true, NB, T>) : go(k_admm4a<O, U_FROM_Z, false, NB, T>);
     };
-    using std::integral_constant;
-    using T1 = integral_constant<bool, true>;
-    using T0 = integral_constant<bool, false>;
-    if (order == 0)
-        return twin ? pick(integral_constant<int, 0>{}, integral_constant<int, 15>{}, T1{})
-                    : pick(integral_constant<int, 0>{}, integral_constant<int, 15>{}, T0{});
-    if (g.nb == 14)
-        return twin ? pick(integral_constant<int, 1>{}, integral_constant<int, 14>{}, T1{})
-                    : pick(integral_constant<int, 1>{}, integral_constant<int, 14>{}, T0{});
-    return twin ? pick(integral_constant<int, 1>{}, integral_constant<int, 15>{}, T1{})
-                : pick(integral_constant<int, 1>{}, integral_constant<int, 15>{}, T0{});
+    using T1 = std::integral_constant<bool, true>;
+    using T0 = std::integral_constant<bool, false>;
+    return dispatch_order_nb<4>(g, order, [&](auto oc, auto nbc) {
+        if constexpr (twin_block(decltype(nbc)::value, 4, decltype(oc)::value) >= 0)
+            if (twin) return pick(oc, nbc, T1{});
+        return pick(oc, nbc, T0{});
+    });
 }
 
 hipError_t launch_gather4b(const Geom& g, int umode, hipStream_t s, double* g_alpha, double* g_u, const double* g_uprev,

@@ -1004,7 +1004,9 @@ mvtv_status problem_create_impl(const mvtv_problem_desc* d, const mvtv_slab_desc
     *out = nullptr;
     if (d->p < 1 || d->p > MVTV_MAX_DIMS) return fail(MVTV_BAD_ARG, "p must be in 1..4");
     if (!d->oty) return fail(MVTV_BAD_ARG, "oty is required");
-    if (d->block_order != MVTV_ORDER_CPP && d->block_order != MVTV_ORDER_PY) return fail(MVTV_BAD_ARG, "block_order");
+    if (d->block_order < MVTV_ORDER_CPP || d->block_order > MVTV_ORDER_PY_NOMINAL) return fail(MVTV_BAD_ARG, "block_order");
+    if (sl && order_nominal(d->block_order))
+        return fail(MVTV_BAD_ARG, "slab decomposition takes the reference difference sets only (MVTV_ORDER_CPP / MVTV_ORDER_PY)");
     const int p = d->p;
     uint64_t N = 1;
     // slab: the mesh is validated (and D built) with the global extent of dim p-1
@@ -1028,7 +1030,7 @@ mvtv_status problem_create_impl(const mvtv_problem_desc* d, const mvtv_slab_desc
     if (N >= (uint64_t(1) << 31)) return fail(MVTV_BAD_ARG, "N >= 2^31 nodes on one GPU");
     const int full = (1 << p) - 1;
     int nb;
-    if (d->block_order == MVTV_ORDER_CPP) nb = full;
+    if ((d->block_order & 1) == MVTV_ORDER_CPP) nb = full;
     else nb = d->weighted ? full - 1 : full;
     if (nb <= 0) return fail(MVTV_BAD_ARG, "empty D (Python create_D with deltas at p = 1)");
     int ndev = mvtv_device_count();
@@ -1055,13 +1057,12 @@ mvtv_status problem_create_impl(const mvtv_problem_desc* d, const mvtv_slab_desc
     P->E = 0;
     for (int k = 0; k < nb; ++k) {
         const int b = block_code(k, p, P->order);
-        const int S = sprime_mask(b, p);
+        const int S = diff_mask(k, p, P->order);
         // reference mixedpartial: a mixed block with min S > 0 multiplies incompatible
-        // matrices unless m_0 == m_{min S} (code/utils.py:102-129)
-        int nominal = 0;
-        for (int j = 0; j < p; ++j)
-            if ((b >> (p - 1 - j)) & 1) nominal |= 1 << j;
-        if (popcount(nominal) >= 2 && !(nominal & 1)) {
+        // matrices unless m_0 == m_{min S} (code/utils.py:102-129); the nominal
+        // orders difference along the block's own dims and take any extents
+        const int nominal = nominal_mask(b, p);
+        if (!order_nominal(P->order) && popcount(nominal) >= 2 && !(nominal & 1)) {
             int lo = 0;
             while (!((nominal >> lo) & 1)) ++lo;
             if (mg[0] != mg[lo]) {

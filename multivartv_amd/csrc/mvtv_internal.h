@@ -7,6 +7,8 @@
 // dim-0-first mixed-partial quirk) and its weight w_k.
 // D^T D is then the sum over subsets S of cS[S] * (tensor product of 1-D Neumann
 // Laplacians over S), cS[S] = sum of w_k^2 over blocks with S'_k == S.
+// Under the nominal block orders (mvtv_block_order 2 and 3) a block's set is its code's own dims
+// instead of S' (diff_mask below); everything else is shared.
 #pragma once
 #include <stdint.h>
 
@@ -14,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <type_traits>
 
 namespace mvtv {
 
@@ -73,24 +76,52 @@ __host__ __device__ constexpr int sprime_mask(int b, int p) {
     return (S & ~(1 << lo)) | 1;
 }
 
-// Binary code of row block k for a given order (0 = C++ create_D, 1 = Python create_D).
+// The dims whose bit is set in binary code b (MSB = dim 0), as a dim-bit mask: the nominal difference set.
+__host__ __device__ constexpr int nominal_mask(int b, int p) {
+    int S = 0;
+    for (int j = 0; j < p; ++j)
+        if ((b >> (p - 1 - j)) & 1) S |= 1 << j;
+    return S;
+}
+
+// Binary code of row block k for a given order: the low bit names the row order (0 = C++ create_D, 1 = Python
+// create_D), bit 1 the difference rule (mvtv_block_order: 2, 3 = the nominal sets).
 __host__ __device__ constexpr int block_code(int k, int p, int order) {
-    return order == 0 ? (k == 0 ? (1 << p) - 1 : k) : k + 1;
+    return (order & 1) == 0 ? (k == 0 ? (1 << p) - 1 : k) : k + 1;
+}
+
+// Difference set of row block k: the reference's S' (orders 0, 1) or the code's own dims (orders 2, 3). Both rules
+// give the same sets for p <= 2, where orders 2 and 3 run the instantiations of 0 and 1 (dispatch_order).
+__host__ __device__ constexpr int diff_mask(int k, int p, int order) {
+    const int b = block_code(k, p, order);
+    return (order & 2) ? nominal_mask(b, p) : sprime_mask(b, p);
+}
+__host__ __device__ constexpr bool order_nominal(int order) { return (order & 2) != 0; }
+// f(std::integral_constant<int, ORD>{}) with the ORD template argument a problem's kernels take: the order itself for
+// P >= 3, its row order (order & 1) for P <= 2, where the nominal instantiations do not exist
+template <int P, class F>
+inline hipError_t dispatch_order(int order, F&& f) {
+    if constexpr (P >= 3) {
+        if (order == 2) return f(std::integral_constant<int, 2>{});
+        if (order == 3) return f(std::integral_constant<int, 3>{});
+    }
+    return (order & 1) == 0 ? f(std::integral_constant<int, 0>{}) : f(std::integral_constant<int, 1>{});
 }
 
 // Twin blocks: under the S' map several codes can share one difference set (3-D: {1,2} -> {0,2}, the rows of {0,2};
 // 4-D: {1,2} -> {0,2}, {1,3}, {2,3} -> {0,3}, {1,2,3} -> {0,2,3}); with equal weights and equal state their alpha, u
 // and z are the same numbers. twin_of(k) is the first block of k's group (k itself for the first), twin_count(k) the
-// size of k's group; twin_block / twin_canon name the first pair (-1: none).
+// size of k's group; twin_block / twin_canon name the first pair (-1: none, as under the nominal orders, whose sets
+// all differ).
 __host__ __device__ constexpr int twin_of(int k, int p, int order) {
     for (int j = 0; j < k; ++j)
-        if (sprime_mask(block_code(k, p, order), p) == sprime_mask(block_code(j, p, order), p)) return j;
+        if (diff_mask(k, p, order) == diff_mask(j, p, order)) return j;
     return k;
 }
 __host__ __device__ constexpr int twin_count(int k, int nb, int p, int order) {
     int n = 0;
     for (int j = 0; j < nb; ++j)
-        if (sprime_mask(block_code(k, p, order), p) == sprime_mask(block_code(j, p, order), p)) ++n;
+        if (diff_mask(k, p, order) == diff_mask(j, p, order)) ++n;
     return n;
 }
 __host__ __device__ constexpr int twin_block(int nb, int p, int order) {

@@ -70,7 +70,7 @@ __global__ __launch_bounds__(kThreads) void k_edge_update(Geom g, const double* 
         }
         static_for<0, NC - 1>([&](auto kc) {
             constexpr int k = decltype(kc)::value;
-            constexpr int S = sprime_mask(block_code(k, P, ORD), P);
+            constexpr int S = diff_mask(k, P, ORD);
             if (k < g.nb) {
                 const double d = g.w[k] * a[S];
                 const uint64_t e = eix(g, k, i);
@@ -110,7 +110,7 @@ __global__ __launch_bounds__(kThreads) void k_gather(Geom g, const double* __res
         double ga = 0.0, gu = 0.0;
         static_for<0, NC - 1>([&](auto kc) {
             constexpr int k = decltype(kc)::value;
-            constexpr int S = sprime_mask(block_code(k, P, ORD), P);
+            constexpr int S = diff_mask(k, P, ORD);
             if (k < g.nb) {
                 double aa = 0.0, au = 0.0;
 #pragma unroll
@@ -178,7 +178,7 @@ __global__ __launch_bounds__(kThreads) void k_apply_D(Geom g, const double* __re
         }
         static_for<0, NC - 1>([&](auto kc) {
             constexpr int k = decltype(kc)::value;
-            constexpr int S = sprime_mask(block_code(k, P, ORD), P);
+            constexpr int S = diff_mask(k, P, ORD);
             if (k < g.nb) edges[eix(g, k, i)] = g.w[k] * a[S];
         });
     }
@@ -192,7 +192,7 @@ __global__ __launch_bounds__(kThreads) void k_edges_fill_valid(Geom g, double* _
         decode<P>(g, i, c);
         static_for<0, NC - 1>([&](auto kc) {
             constexpr int k = decltype(kc)::value;
-            constexpr int S = sprime_mask(block_code(k, P, ORD), P);
+            constexpr int S = diff_mask(k, P, ORD);
             if (k < g.nb) {
                 bool valid = true;
 #pragma unroll
@@ -547,7 +547,7 @@ __global__ __launch_bounds__(kThreads) void k_dmaxabs(Geom g, const double* __re
                 if (!((T >> j) & 1)) a[T | (1 << j)] = a[T] - a[T | (1 << j)];
         static_for<0, NC - 1>([&](auto kc) {
             constexpr int k = decltype(kc)::value;
-            constexpr int S = sprime_mask(block_code(k, P, ORD), P);
+            constexpr int S = diff_mask(k, P, ORD);
             if (k < g.nb) red[0] = fmax(red[0], fabs(g.w[k] * a[S]));
         });
     }
@@ -719,7 +719,7 @@ hipError_t dispatch_w(int wmode, F&& f) {
 RedDims red_dims(const Geom& g, int order, int k) {
     RedDims r{};
     r.p = g.p;
-    const int S = sprime_mask(block_code(k, g.p, order), g.p);
+    const int S = diff_mask(k, g.p, order);
     for (int j = 0; j < g.p; ++j) {
         r.rd[j] = g.m[j] - ((S >> j) & 1);
         r.stride[j] = g.stride[j];
@@ -747,14 +747,12 @@ hipError_t launch_edge_update(const Geom& g, int order, int umode, const Launch&
             return hipGetLastError();
         };
         const bool dth = theta_old != nullptr;
-        if (order == 0) {
+        return dispatch_order<P>(order, [&](auto oc) {
+            constexpr int O = decltype(oc)::value;
             if (umode == U_EXPLICIT)
-                return dth ? go(k_edge_update<P, 0, U_EXPLICIT, true>) : go(k_edge_update<P, 0, U_EXPLICIT, false>);
-            return dth ? go(k_edge_update<P, 0, U_FROM_Z, true>) : go(k_edge_update<P, 0, U_FROM_Z, false>);
-        }
-        if (umode == U_EXPLICIT)
-            return dth ? go(k_edge_update<P, 1, U_EXPLICIT, true>) : go(k_edge_update<P, 1, U_EXPLICIT, false>);
-        return dth ? go(k_edge_update<P, 1, U_FROM_Z, true>) : go(k_edge_update<P, 1, U_FROM_Z, false>);
+                return dth ? go(k_edge_update<P, O, U_EXPLICIT, true>) : go(k_edge_update<P, O, U_EXPLICIT, false>);
+            return dth ? go(k_edge_update<P, O, U_FROM_Z, true>) : go(k_edge_update<P, O, U_FROM_Z, false>);
+        });
     });
 }
 
@@ -769,34 +767,32 @@ hipError_t launch_gather(const Geom& g, int order, int umode, const Launch& L, c
             return hipGetLastError();
         };
         const bool prev = g_uprev != nullptr;
-        if (order == 0) {
-            if (umode == U_EXPLICIT) return prev ? go(k_gather<P, 0, U_EXPLICIT, true>) : go(k_gather<P, 0, U_EXPLICIT, false>);
-            return prev ? go(k_gather<P, 0, U_FROM_Z, true>) : go(k_gather<P, 0, U_FROM_Z, false>);
-        }
-        if (umode == U_EXPLICIT) return prev ? go(k_gather<P, 1, U_EXPLICIT, true>) : go(k_gather<P, 1, U_EXPLICIT, false>);
-        return prev ? go(k_gather<P, 1, U_FROM_Z, true>) : go(k_gather<P, 1, U_FROM_Z, false>);
+        return dispatch_order<P>(order, [&](auto oc) {
+            constexpr int O = decltype(oc)::value;
+            if (umode == U_EXPLICIT) return prev ? go(k_gather<P, O, U_EXPLICIT, true>) : go(k_gather<P, O, U_EXPLICIT, false>);
+            return prev ? go(k_gather<P, O, U_FROM_Z, true>) : go(k_gather<P, O, U_FROM_Z, false>);
+        });
     });
 }
 
 hipError_t launch_apply_D_padded(const Geom& g, int order, const Launch& L, const double* theta, double* edges) {
     return dispatch_p(g.p, [&](auto pc) {
         constexpr int P = decltype(pc)::value;
-        if (order == 0)
-            klaunch((k_apply_D<P, 0>), dim3(L.grid), dim3(kThreads), 0, L.stream, g, theta, edges);
-        else
-            klaunch((k_apply_D<P, 1>), dim3(L.grid), dim3(kThreads), 0, L.stream, g, theta, edges);
-        return hipGetLastError();
+        return dispatch_order<P>(order, [&](auto oc) {
+            klaunch((k_apply_D<P, decltype(oc)::value>), dim3(L.grid), dim3(kThreads), 0, L.stream, g, theta, edges);
+            return hipGetLastError();
+        });
     });
 }
 
 hipError_t launch_edges_fill_valid(const Geom& g, int order, const Launch& L, double* edges, double value) {
     return dispatch_p(g.p, [&](auto pc) {
         constexpr int P = decltype(pc)::value;
-        if (order == 0)
-            klaunch((k_edges_fill_valid<P, 0>), dim3(L.grid), dim3(kThreads), 0, L.stream, g, edges, value);
-        else
-            klaunch((k_edges_fill_valid<P, 1>), dim3(L.grid), dim3(kThreads), 0, L.stream, g, edges, value);
-        return hipGetLastError();
+        return dispatch_order<P>(order, [&](auto oc) {
+            klaunch((k_edges_fill_valid<P, decltype(oc)::value>), dim3(L.grid), dim3(kThreads), 0, L.stream, g, edges,
+                    value);
+            return hipGetLastError();
+        });
     });
 }
 
@@ -913,9 +909,10 @@ hipError_t launch_cg_vec(const Geom& g, const Launch& L, int op, double coef, do
 hipError_t launch_dmaxabs(const Geom& g, int order, const Launch& L, const double* x, double* partials) {
     return dispatch_p(g.p, [&](auto pc) {
         constexpr int P = decltype(pc)::value;
-        if (order == 0) klaunch(k_dmaxabs<P, 0>, dim3(L.grid), dim3(kThreads), 0, L.stream, g, x, partials);
-        else klaunch(k_dmaxabs<P, 1>, dim3(L.grid), dim3(kThreads), 0, L.stream, g, x, partials);
-        return hipGetLastError();
+        return dispatch_order<P>(order, [&](auto oc) {
+            klaunch((k_dmaxabs<P, decltype(oc)::value>), dim3(L.grid), dim3(kThreads), 0, L.stream, g, x, partials);
+            return hipGetLastError();
+        });
     });
 }
 

@@ -13,6 +13,8 @@
 // `mvtv_mbs --batched[=MODE] <input> <output>`: the same mbs_impl with mbs_impl_options::batched, the whole CV as one
 // mvtv_cv_batch call (meshes of at most 4096 nodes, p = 4: 1296); MODE is the batch_cosine mode 0, 1 or 2 (default 0).
 // Same input and output formats.
+// `mvtv_mbs --nominal [--batched[=MODE]] <input> <output>`: mbs_impl_options::nominal, true mixed partials
+// (MVTV_ORDER_CPP_NOMINAL): a 3-D or 4-D mesh of any extents.
 //
 // `mvtv_mbs --cpp <input> <output>`: variant A's mbs (cpp-code/solvers.cpp:277-310) instead. Same input
 // (hdr[6] = 1 selects the corrected CV, 0 the reference's); output:
@@ -36,9 +38,15 @@ void wr(std::FILE* f, const T* v, size_t n) { std::fwrite(v, sizeof(T), n, f); }
 
 int main(int argc, char** argv) {
     int mode = 0;   // 0 mbs_impl (B), 1 mbs (A), 2 mbs_one without cache (A)
+    mvtv::mbs_impl_options bopt;
+    if (argc >= 4 && std::string(argv[1]) == "--nominal") {
+        bopt.nominal = true;
+        argv[1] = argv[0];
+        ++argv;
+        --argc;
+    }
     if (argc == 4 && std::string(argv[1]) == "--cpp") mode = 1;
     if (argc == 4 && std::string(argv[1]) == "--cpp-one") mode = 2;
-    mvtv::mbs_impl_options bopt;
     if (argc == 4 && std::string(argv[1]).rfind("--batched", 0) == 0) {
         const std::string a = argv[1];
         bopt.batched = true;
@@ -49,8 +57,8 @@ int main(int argc, char** argv) {
         ++argv;
         --argc;
     }
-    if (argc != 3) {
-        std::fprintf(stderr, "usage: %s [--cpp | --cpp-one | --batched[=0|1|2]] <input> <output>\n", argv[0]);
+    if (argc != 3 || (mode && bopt.nominal)) {   // variant A keeps the reference rule
+        std::fprintf(stderr, "usage: %s [--cpp | --cpp-one | [--nominal] [--batched[=0|1|2]]] <input> <output>\n", argv[0]);
         return 2;
     }
     std::FILE* in = std::fopen(argv[1], "rb");

@@ -3643,8 +3643,10 @@ hipError_t launch_plane_pass(const SpecPlan& sp, const Geom& g, hipStream_t s, i
 }
 
 // The marching line sweeps (k_sweep): shapes with an instantiation
+// (m0 = m1: every 3-D mesh of the reference orders; the sweeps have not run on m0 != 512, which only a nominal
+// order admits, so such a mesh keeps the per-dimension passes: DESIGN §8)
 bool line_sweep_shape_ok(const Geom& g) {
-    return g.p == 3 && g.m[1] == 512u && g.m[0] % 16u == 0u && g.m[2] >= 2u;
+    return g.p == 3 && g.m[1] == 512u && g.m[0] == g.m[1] && g.m[0] % 16u == 0u && g.m[2] >= 2u;
 }
 
 // Chunk count of the sweeps: the grid runs in rounds of the resident workgroups (occupancy x CUs), and a round lasts

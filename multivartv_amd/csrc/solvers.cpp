@@ -186,7 +186,8 @@ void build_cache(const mat& data, const vec& y, const mat& mesh, const vec& m, c
     if (!deltas.empty() && deltas.size() != dims.size()) throw std::invalid_argument("deltas must have p values");
     const auto axes = tensor_axes(mesh, dims);
     // the same mesh and D (CV folds): new data only
-    const bool reuse = cache.prob && cache.ntheta == N && cache.deltas == deltas;
+    const int order = cache.nominal ? MVTV_ORDER_CPP_NOMINAL : MVTV_ORDER_CPP;
+    const bool reuse = cache.prob && cache.ntheta == N && cache.deltas == deltas && cache.prob_order == order;
     if (!reuse) {
         if (cache.prob) mvtv_problem_destroy(cache.prob);
         cache.prob = nullptr;
@@ -196,7 +197,7 @@ void build_cache(const mat& data, const vec& y, const mat& mesh, const vec& m, c
             d.m[j] = dims[j];
             d.deltas[j] = deltas.empty() ? 1.0 : deltas[j];
         }
-        d.block_order = MVTV_ORDER_CPP;
+        d.block_order = order;
         d.weighted = deltas.empty() ? 0 : 1;
         const vec zeros(size_t(N), 0.0);
         d.oty = zeros.data();
@@ -205,6 +206,7 @@ void build_cache(const mat& data, const vec& y, const mat& mesh, const vec& m, c
         cache.ntheta = N;
         cache.rowsD = mvtv_problem_edges(cache.prob);
         cache.deltas = deltas;
+        cache.prob_order = order;
     }
     cache.oidx.assign(size_t(data.n_rows), 0);
     if (!axes.empty()) {
@@ -462,6 +464,7 @@ mbs_impl_result mbs_impl(const mat& data, const vec& y, const vec& m, const mat*
     const mat MESH = mesh ? *mesh : create_mesh(data, m);
     const vec deltas = create_deltas(data, m);
     mbs_cache cache;
+    cache.nominal = options && options->nominal;
     create_cache_objects(data, y, MESH, m, deltas, cache, device);
     R.lambdas = create_lambdas(n_lambda, cache, lambdas, verbose);
     const int nl = int(R.lambdas.size());

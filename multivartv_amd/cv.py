@@ -78,7 +78,7 @@ def tensor_axes(mesh, m):
     return axes if ok else None
 
 
-def _cache(mesh, m, deltas, x, yy, device, problem=None, axes=None):
+def _cache(mesh, m, deltas, x, yy, device, problem=None, axes=None, order=_lib.ORDER_CPP):
     """create_cache_objects (rcpp…/solvers.cpp:36-44): O from the nearest mesh point -> W, O^T y.
 
     On a tensor mesh (always, for create_mesh) O, diag(O^T O) and O^T y are built on the GPU
@@ -86,13 +86,13 @@ def _cache(mesh, m, deltas, x, yy, device, problem=None, axes=None):
     N = int(np.prod(m))
     if axes is not None:
         if problem is None:
-            problem = _lib.Problem(m, np.zeros(N), deltas=deltas, order=_lib.ORDER_CPP, weighted=True, device=device)
+            problem = _lib.Problem(m, np.zeros(N), deltas=deltas, order=order, weighted=True, device=device)
         return problem, problem.set_scattered(axes, x, yy)
     idx = nearest_index(x, mesh)
     W, oty = interp_weights(idx, N, yy)
     wdiag = None if np.all(W == 1.0) else W
     if problem is None:
-        problem = _lib.Problem(m, oty, wdiag=wdiag, deltas=deltas, order=_lib.ORDER_CPP, weighted=True, device=device)
+        problem = _lib.Problem(m, oty, wdiag=wdiag, deltas=deltas, order=order, weighted=True, device=device)
     else:
         problem.set_data(oty, wdiag)   # the same mesh: CV folds re-run create_cache_objects (:347-348)
     return problem, idx
@@ -136,7 +136,7 @@ def assign(n_items: int, world: int, rank: int):
 
 
 def mbs_impl(data, y, m, mesh=None, n_lambda=100, ftrue=None, lambdas=None, folds=1, verbose=False, seed=0,
-             device=None, group=None, _runner=None, concurrent=1, batched=False, batch_cosine=0, device_cv=False):
+             device=None, group=None, _runner=None, concurrent=1, batched=False, batch_cosine=0, device_cv=False, nominal=False):
     """rcpp…/solvers.cpp:305-376. Returns the reference's result list as a dict (rank 0; other
     ranks return only 'cv.mses' and 'lambda_minmse_ind').
 
@@ -158,6 +158,10 @@ def mbs_impl(data, y, m, mesh=None, n_lambda=100, ftrue=None, lambdas=None, fold
     in as theta_0, so the fits are those of ``batched=True``. Selection, the folds == 1 refit and the result dict are
     unchanged. ValueError without ``batched``, for a ``mesh`` that is not a tensor product, with more than one rank,
     with ``_runner``, or on a mesh ``Problem.batch_ok`` refuses.
+
+    ``nominal``: every problem of the run (unbatched, ``concurrent``, ``batched`` and ``device_cv`` alike) is built
+    with ``ORDER_CPP_NOMINAL``: block b differences along exactly the dims of its code, so a 3-D or 4-D mesh of any
+    extents is accepted (the default, the reference's rule, refuses m_0 != m_1). For p <= 2 the results are the same.
     """
     data = np.asarray(data, dtype=np.float64)
     if data.ndim == 1:
@@ -175,6 +179,7 @@ def mbs_impl(data, y, m, mesh=None, n_lambda=100, ftrue=None, lambdas=None, fold
 
     state = {}
     AXES = tensor_axes(MESH, m)
+    ORDER = _lib.ORDER_CPP_NOMINAL if nominal else _lib.ORDER_CPP
 
     import threading
     lock = threading.Lock()
@@ -182,9 +187,9 @@ def mbs_impl(data, y, m, mesh=None, n_lambda=100, ftrue=None, lambdas=None, fold
     def problem_for(x, yy, own=False):
         """The rank's shared problem (set to this data), or with own=True a new one (concurrent items)."""
         if own:
-            return _cache(MESH, m, deltas, x, yy, device, None, AXES)
+            return _cache(MESH, m, deltas, x, yy, device, None, AXES, ORDER)
         with lock:
-            P, idx = _cache(MESH, m, deltas, x, yy, device, state.get("P"), AXES)
+            P, idx = _cache(MESH, m, deltas, x, yy, device, state.get("P"), AXES, ORDER)
             state["P"] = P
         return P, idx
 
